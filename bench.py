@@ -36,8 +36,16 @@ epoch's refill, as in the timed region);
 mgx_gae_dones alone at the horizon and at T=1024 (17 B per element).
 `cpu_baseline` times the C port of the env (oracle/) on this host's cores.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   (N>1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step`, `window` and the
+device-clock `roofline` of the timed launches.  --full adds everything that takes runs of its own: `cpu_baseline`,
+the other layouts, the roofline's probe launches and the committed rocprofv3 figures (`traffic`, `rocprof`), `gae`,
+`steady_state`, and the ppo workload's evaluation.  --dump-outputs DIR writes, after the timed steps, what the
+last timed horizon left in the rollout buffers as DIR/<name>.npy (a fixed sample of 1,024 envs; the inputs --
+env seeds and the actions' counter-based draws -- are the same from run to run, so two builds compare array
+for array).
 
   python bench.py --workload ppo [--steps K] [--warmup W]
   BASELINE config 3: the full PPO loop (PKP 8x8, 65,536 envs/GPU, PyTorch policy,
@@ -68,6 +76,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (rollout 2048; ppo: PPO iterations, 4)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps (rollout 128; ppo: 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline: the CPU baseline (--cpu-seconds), the other layouts "
+                         "(--both-layouts), the roofline probe (--probe), the GAE probes, the steady_state window "
+                         "(--steady-ms), the committed rocprofv3 figures, ppo's evaluation (--eval-episodes); a plain "
+                         "run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them left in the rollout buffers (a fixed "
+                         "sample of envs, see dump_outputs) as DIR/<name>.npy")
     ap.add_argument("--n-envs", type=int, default=65536, help="envs per GPU")
     ap.add_argument("--problem", default="multi")
     ap.add_argument("--mission", default="5")
@@ -133,6 +149,8 @@ def parse():
     for k, v in presets[args.config].items():          # a preset fills what was not given explicitly
         if getattr(args, k) == ap.get_default(k):
             setattr(args, k, v)
+    if not args.full:                                  # a plain run: the headline's own steps and nothing beside them
+        args.cpu_seconds, args.both_layouts, args.steady_ms, args.eval_episodes = 0.0, 0, 0.0, 0
     ppo = args.workload == "ppo"
     if args.steps is None:
         args.steps = 4 if ppo else 2048
@@ -292,10 +310,11 @@ def main_ppo(args, world, rank, local, dev, ranks_seen=1):
     col.start()
     K, W = args.steps, args.warmup
     total = (K + W) * n * cfg.horizon * world
+    last = {}                                         # the last iteration's rollout (--dump-outputs)
 
     def iteration():
         t0 = time.perf_counter()
-        buf = col.collect()
+        buf = last["buf"] = col.collect()
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
         tr.global_adv_stats(buf)
@@ -326,6 +345,14 @@ def main_ppo(args, world, rank, local, dev, ranks_seen=1):
         wall = _allreduce(wall, dist.ReduceOp.MAX)
     eng.poll_error()
     wall = float(wall[0])
+    outs = None
+    if rank == 0 and args.dump_outputs:               # the last iteration's rollout, for the sampled envs
+        ix, buf = dump_envs(n, dev), last["buf"]
+        arrays = {k: getattr(buf, k)[:, ix] for k in ("actions", "rewards", "values", "log_probs", "advantages",
+                                                      "returns")}
+        outs = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, dict(arrays, env_index=ix)),
+                "note": "the last PPO iteration's [horizon, envs] rollout for %d envs sampled with a fixed seed "
+                        "(env_index); the policy trains between iterations" % len(ix)}
     ev = None
     if rank == 0 and args.eval_episodes > 0:          # untimed: learning evidence for the trained policy
         ev = _ppo_success(pol, cfg.env, args.eval_episodes, dev)
@@ -347,6 +374,8 @@ def main_ppo(args, world, rank, local, dev, ranks_seen=1):
                        "parallelism": "env-sharded dp%d" % world, "host_wait": getattr(args, "host_wait_applied", "auto")},
             "phases_s_per_iter": {"collect": tc / K, "train": tt / K},
             "eval": ev,
+            "outputs": outs,
+            "full": args.full,
             "roofline": None,
             "ranks_seen": ranks_seen, "dist_backend": dist.get_backend() if world > 1 else None,
         }), flush=True)
@@ -489,9 +518,32 @@ def gae_probe(dev, n, T, reps=20):
             "frac": b / us / 1e3 / PEAK_HBM_GBPS, "unit": "GB/s"}
 
 
-def measure_rollout(args, layout, world, rank, dev):
+DUMP_ENVS = 1024                # --dump-outputs: envs sampled (fixed seed), every horizon step of each
+DUMP_OBS_STEPS = 16             # ... and the observations after the last this-many steps
+
+
+def dump_envs(n, dev):
+    """--dump-outputs: the env sample, min(n, 1,024) indices drawn once with a fixed seed, ascending."""
+    ix = np.sort(np.random.default_rng(20260).choice(n, size=min(n, DUMP_ENVS), replace=False))
+    return torch.as_tensor(ix, dtype=torch.int64, device=dev)
+
+
+def dump_outputs(path, arrays):
+    """Write {name: device tensor} as path/<name>.npy, float64 for f64 tensors and float32 for everything else
+    (u8 rows and flags are exact in f32); returns {name: shape}."""
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
+def measure_rollout(args, layout, world, rank, dev, dump=None):
     """One rollout measurement (the timed region of the module docstring) on a fresh engine;
-    returns the JSON dict on rank 0."""
+    returns the JSON dict on rank 0.  dump: a dict that receives what the last timed horizon left in the
+    rollout buffers (--dump-outputs), copied right after the region."""
     from mgx import MgxEngine, gae_dones
     n = args.n_envs
     mission = None if args.mission == "None" else int(args.mission)
@@ -515,8 +567,9 @@ def measure_rollout(args, layout, world, rank, dev):
     eng.enable_clock(slots=(W + 3 * K + args.probe) // per0 + 64)     # every step-kernel launch of this run
     g = torch.Generator(device=dev)
     g.manual_seed(1234 + rank)
-    P = args.probe
-    actions = torch.randint(0, 7, (W + K + P, n), device=dev, generator=g, dtype=torch.int32)
+    P = args.probe if args.full else 0                   # probe launches after the region (--full)
+    # (the table holds the probe's rows either way: the synthetic values `g` draws next do not depend on --full)
+    actions = torch.randint(0, 7, (W + K + args.probe, n), device=dev, generator=g, dtype=torch.int32)
     # rollout storage the steps write directly (compact layout): reward f32 and done u8 per step;
     # values are synthetic (the rollout bench has no policy); GAE + the (sum A, sum A^2, n)
     # all-reduce run once per horizon inside the timed region
@@ -595,6 +648,7 @@ def measure_rollout(args, layout, world, rank, dev):
                                                          # pays for every refill it forked
 
     graphs = []
+    gblocks = []                                         # the ring block each graph writes (--dump-outputs)
     replay_cycles = 1                                    # untimed replays of the graph set (warm-up)
     forks0 = eng.stats()["refill_launches"]
     # ring buffer: graph c writes block (c0 + c + 1) % m; replayed in cyclic order, the graphs continue the
@@ -639,6 +693,7 @@ def measure_rollout(args, layout, world, rank, dev):
                     values=vals, last_values=last_v, gamma=gamma, gae_lambda=lam, out=(adv, ret),
                     stats=hist[c % nchunks], scratch=scratch))
                 graphs.append(_PreparedChunk(cbuf, cbuf.block, fn, eng, sp))
+                gblocks.append(cbuf.block)
         else:
             with torch.cuda.stream(s):
                 for c in range(ng):
@@ -649,6 +704,7 @@ def measure_rollout(args, layout, world, rank, dev):
                         random_actions(abuf[c], act_ctr, seed=act_seed)
                     gr.capture_end()
                     graphs.append(gr)
+                    gblocks.append(cbuf.block if compact else 0)
         # one untimed replay of each graph (more warm-up steps: every graph is whole refill epochs
         # ending in a join): the first launch of an instantiated graph pays its upload, ~0.1 ms
         # that a 20-step window would otherwise count as 5 us per step
@@ -709,6 +765,25 @@ def measure_rollout(args, layout, world, rank, dev):
         torch.cuda._sleep(1000)                          # trace marker: the region ended
         torch.cuda.synchronize(dev)
     gpu_ms = ev0.elapsed_time(ev1)
+    if dump is not None:
+        # what the region's last horizon (its last graph, or the last eager chunk) left behind, for the sampled
+        # envs: every step's reward, done, advantage and return, the horizon's (sum A, sum A^2, n), and the
+        # observations after its last steps -- rows + mission ids (compact layouts) or the stacks after the last step
+        ix = dump_envs(n, dev)
+        dump.update(env_index=ix, rewards=rew[:, ix], advantages=adv[:, ix], returns=ret[:, ix],
+                    adv_stats=hist[nchunks - 1].clone())
+        if compact:
+            b = gblocks[nchunks - 1] if graphs else cbuf.block
+            dump["dones"] = cbuf.starts[b * H:b * H + H][:, ix]
+            r = torch.as_tensor([(b * H + t - 1) % cbuf.R for t in range(max(1, H - DUMP_OBS_STEPS + 1), H + 1)],
+                                dtype=torch.int64, device=dev)
+            dump["obs_rows"] = cbuf.rows[r[:, None], ix[None, :]]
+            dump["mission_ids"] = cbuf.mids[r[:, None], ix[None, :]]
+        else:
+            dump["dones"] = dones[:, ix]
+            for k, v in eng.obs.items():
+                dump["obs_" + k] = v[ix]
+        torch.cuda.synchronize(dev)
     clk1 = (eng.clock_launches(scls), eng.clock_launches(1), eng.clock_launches(2))
     timed_step_us = eng.clock_spans_us(scls, clk0[0], clk1[0])   # the timed region's own kernel launches
     timed_refill_us = eng.clock_spans_us(1, clk0[1], clk1[1])
@@ -727,7 +802,7 @@ def measure_rollout(args, layout, world, rank, dev):
         # before the window opens, so the window holds the epoch's fork and the kernel.  A spin kernel
         # first keeps the GPU busy while the host enqueues every window (round 4: without it each window
         # also held the host's time to enqueue the refill ahead of the rollout, ~19 us per launch)
-        if hasattr(torch.cuda, "_sleep"):
+        if P >= E and hasattr(torch.cuda, "_sleep"):
             torch.cuda._sleep(int((P // E) * 60e-6 * 2.4e9))
         for t in range(0, P - P % E, E):
             eng.join()
@@ -746,7 +821,7 @@ def measure_rollout(args, layout, world, rank, dev):
     # the host enqueues the probe's launches one by one (~15 us of Python per step, about the
     # kernel's own time): a spin kernel first keeps the GPU busy until they are all queued, so
     # the windows time back-to-back launches, not the host
-    if hasattr(torch.cuda, "_sleep"):
+    if P and hasattr(torch.cuda, "_sleep"):
         torch.cuda._sleep(int(P * 40e-6 * 2.4e9))
     for t in range(P):
         if eng.epoch_boundary():
@@ -785,8 +860,10 @@ def measure_rollout(args, layout, world, rank, dev):
     assert int(total_env_steps) == n * K * world, (total_env_steps, n * K * world)
     hs = hist.cpu().numpy()
     assert abs(hs[:, 2].sum() - float(H) * n * world * nchunks) < 0.5, hs    # every chunk's GAE ran
-    gae_h = gae_probe(dev, n, H)
-    gae_1k = gae_probe(dev, n, 1024) if H != 1024 else gae_h
+    gae_h = gae_1k = None                                # (--full: mgx_gae_dones timed alone)
+    if args.full:
+        gae_h = gae_probe(dev, n, H)
+        gae_1k = gae_probe(dev, n, 1024) if H != 1024 else gae_h
     # Steady state (round 5, reported beside the headline, N = 1): the same graphs after --steady-ms more of
     # untimed replays, then several timed replays.  The region above follows mgx_reset by a few hundred steps, when
     # every ring is still nearly full; over thousands of steps a few rings drain to the 2K floor and their waves
@@ -847,7 +924,7 @@ def measure_rollout(args, layout, world, rank, dev):
         # clock (first workgroup start -> last workgroup end of each launch; the max over ranks)
         per_launch_s = step_us_max * 1e-6
         achieved = b_alg / per_launch_s / 1e9
-        prof_dir, lib_sha = _profile_dir()
+        prof_dir, lib_sha = _profile_dir() if args.full else (None, None)   # (the committed rocprofv3 figures)
         traffic, traffic_src = None, None
         spl = per
         if prof_dir is not None:
@@ -980,10 +1057,11 @@ def measure_rollout(args, layout, world, rank, dev):
                          "traffic_frac": (traffic / per_launch_s / 1e9 / PEAK_HBM_GBPS) if traffic else None,
                          "stack_bytes_per_launch": stack_bytes,
                          "achieved_incl_stack": (b_alg + stack_bytes) / per_launch_s / 1e9},
-            "gae": {"horizon": gae_h, "T1024": gae_1k},
+            "gae": {"horizon": gae_h, "T1024": gae_1k} if args.full else None,
             "steady_state": dict(steady, ratio_to_value=steady["value"] / (total_env_steps / wall_max))
                             if steady else None,
             "gpu_time_ms": gpu_max * 1e3,
+            "full": args.full,
         }
         return out
     return None
@@ -1025,7 +1103,15 @@ def main():
         ranks_seen = int(round(float(ones[0])))
     if args.workload == "ppo":
         return main_ppo(args, world, rank, local, dev, ranks_seen)
-    out = measure_rollout(args, args.layout, world, rank, dev)
+    dump = {} if args.dump_outputs and rank == 0 else None
+    out = measure_rollout(args, args.layout, world, rank, dev, dump)
+    if dump is not None:
+        out["outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, dump),
+                          "note": "what the last timed horizon left in the rollout buffers, for %d envs sampled with a "
+                                  "fixed seed (env_index): [horizon, envs] rewards / dones / advantages / returns, "
+                                  "adv_stats = its (sum A, sum A^2, n), and the observations after its last <= %d "
+                                  "steps" % (len(dump["env_index"]), DUMP_OBS_STEPS)}
+        dump.clear()
     if world == 1 and args.both_layouts:
         # the other observation layouts on the same workload, reported beside the headline: one launch
         # per step (compact rows: the path a policy in the loop takes) and the materialised SB3 stacks

@@ -51,6 +51,42 @@ def test_committed_profiles_reproduce_the_driver_line_roofline():
                                           "mgx_rollout_kernel", 10 ** 6, 1) is None
 
 
+def test_plain_run_keeps_only_the_headline_and_full_restores_the_rest():
+    """A plain run switches off everything that takes runs of its own; --full leaves every option as given."""
+    sys.argv = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"]
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 20 and a.layout == "fused"
+    assert (a.cpu_seconds, a.both_layouts, a.steady_ms, a.eval_episodes) == (0, 0, 0, 0)
+    sys.argv += ["--full", "--dump-outputs", "out"]
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out" and a.steps == 20 and a.layout == "fused"
+    assert (a.cpu_seconds, a.both_layouts, a.steady_ms, a.eval_episodes) == (10.0, 1, 400.0, 100)
+    sys.argv += ["--cpu-seconds", "0", "--both-layouts", "0"]
+    a = bench.parse()
+    assert (a.cpu_seconds, a.both_layouts, a.steady_ms) == (0, 0, 400.0)
+
+
+def test_dump_outputs_sample_is_fixed_and_arrays_are_float(tmp_path):
+    """--dump-outputs: the env sample is the same in every run (ascending, distinct, at most 1,024), and every
+    array is written as float32 -- float64 only for f64 tensors -- with integer values kept exactly."""
+    import numpy as np
+    import torch
+    ix = bench.dump_envs(65536, "cpu")
+    assert torch.equal(ix, bench.dump_envs(65536, "cpu")) and ix.dtype == torch.int64
+    assert len(ix) == 1024 and bool((ix[1:] > ix[:-1]).all()) and 0 <= int(ix[0]) and int(ix[-1]) < 65536
+    assert torch.equal(bench.dump_envs(64, "cpu"), torch.arange(64))
+    rows = torch.arange(2 * 3 * 148, dtype=torch.int64).reshape(2, 3, 148).to(torch.uint8)
+    stats = torch.tensor([1.0 / 3.0, 2.0, 3.0], dtype=torch.float64)
+    shapes = bench.dump_outputs(str(tmp_path / "d"), {"obs_rows": rows, "adv_stats": stats, "env_index": ix})
+    assert shapes == {"obs_rows": [2, 3, 148], "adv_stats": [3], "env_index": [1024]}
+    r = np.load(tmp_path / "d" / "obs_rows.npy")
+    assert r.dtype == np.float32 and np.array_equal(r, rows.numpy())
+    s = np.load(tmp_path / "d" / "adv_stats.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, stats.numpy())
+    e = np.load(tmp_path / "d" / "env_index.npy")
+    assert e.dtype == np.float32 and np.array_equal(e, ix.numpy())
+
+
 def test_host_wait_modes_and_defaults():
     """bench.py's defaults (round 5): spin-waiting host, GAE fused into the rollout launch; an unknown wait mode
     is refused before anything touches the HIP runtime."""

@@ -14,7 +14,7 @@ for r in $(seq 1 ${ROUNDS:-3}); do
   for i in $(seq 0 $((NL - 1))); do
     V=${ARR[$(( (i + r - 1) % NL ))]}
     ( [ "$V" != "-" ] && export $V
-      timeout -k 10 ${BENCH_TIMEOUT:-240} python bench.py ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5} --cpu-seconds 0 --both-layouts 0 \
+      timeout -k 10 ${BENCH_TIMEOUT:-240} python bench.py --full ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5} --cpu-seconds 0 --both-layouts 0 \
         > $O/abe_line.json 2> $O/abe_err.log ) || { tail -20 $O/abe_err.log; exit 1; }
     python -c "import json,sys; d=json.load(open('$O/abe_line.json')); r=d['roofline']; f=r.get('refill') or {}; s=d.get('steady_state') or {}; print('[$V]', '%.3e'%d['value'], 'steady %.3e'%s.get('value',0), 'gpu_ms=%s'%d.get('gpu_time_ms'), 'kern_us=%.2f'%r['avg_launch_us'], 'refill_us=%.1f'%f.get('avg_launch_us', 0))" | tee -a $O/abe_${TAG:-x}.txt
     python -c "import json; d=json.load(open('$O/abe_line.json')); d['variant']='$V'; print(json.dumps(d))" >> $O/abe_${TAG:-x}.jsonl

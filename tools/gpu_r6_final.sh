@@ -17,14 +17,14 @@ for k in ('compact_layout','sb3_layout'):
     if k in d: print('  ', k, '%.3e' % d[k]['value'], 'frac %.3f' % d[k]['roofline']['frac'])
 "; }
 for i in 1 2; do
-  timeout -k 10 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_$i.json 2> $O/driver_$i.err || { tail -20 $O/driver_$i.err; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/driver_$i.json 2> $O/driver_$i.err || { tail -20 $O/driver_$i.err; exit 1; }
   summ $O/driver_$i.json
 done
-timeout -k 10 300 python -u bench.py --cpu-seconds 0 --both-layouts 0 > $O/default.json 2> $O/default.err || { tail -20 $O/default.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --cpu-seconds 0 --both-layouts 0 > $O/default.json 2> $O/default.err || { tail -20 $O/default.err; exit 1; }
 summ $O/default.json
-timeout -k 10 300 python -u bench.py --config 4 --cpu-seconds 0 --both-layouts 0 > $O/cfg4.json 2> $O/cfg4.err || { tail -20 $O/cfg4.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --config 4 --cpu-seconds 0 --both-layouts 0 > $O/cfg4.json 2> $O/cfg4.err || { tail -20 $O/cfg4.err; exit 1; }
 summ $O/cfg4.json
-timeout -k 10 300 python -u bench.py --config 5 --cpu-seconds 0 --both-layouts 0 > $O/cfg5.json 2> $O/cfg5.err || { tail -20 $O/cfg5.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --config 5 --cpu-seconds 0 --both-layouts 0 > $O/cfg5.json 2> $O/cfg5.err || { tail -20 $O/cfg5.err; exit 1; }
 summ $O/cfg5.json
-timeout -k 10 400 python -u bench.py --workload ppo --steps 2 --warmup 1 --horizon 16 --cpu-seconds 0 > $O/ppo16.json 2> $O/ppo16.err || { tail -20 $O/ppo16.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full --workload ppo --steps 2 --warmup 1 --horizon 16 --cpu-seconds 0 > $O/ppo16.json 2> $O/ppo16.err || { tail -20 $O/ppo16.err; exit 1; }
 summ $O/ppo16.json

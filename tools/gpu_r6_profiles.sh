@@ -16,9 +16,9 @@ for shape in ${SHAPES:-2:fused:20 2:fused:2048 2:compact:20 4:fused:2048 5:fused
   IFS=: read cfg lay steps <<< "$shape"
   if [ $steps -eq 20 ]; then E=20; else E=64; fi
   tag=${cfg}_${lay}_e$E
-  B="$R/bench.py --config $cfg --layout $lay --both-layouts 0 --cpu-seconds 0 --steps $steps --warmup 5"
+  B="$R/bench.py --full --config $cfg --layout $lay --both-layouts 0 --cpu-seconds 0 --steps $steps --warmup 5"
   # the driver's own command, unchanged, for its line (config 2, fused, 20 steps)
-  [ "$shape" = "2:fused:20" ] && B="$R/bench.py --gpus 1 --steps 20 --warmup 5"
+  [ "$shape" = "2:fused:20" ] && B="$R/bench.py --full --gpus 1 --steps 20 --warmup 5"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/s_$tag -o run --output-format csv -- python3 $B > $O/s_$tag.log 2>&1 || { tail -20 $O/s_$tag.log; exit 1; }
   cp $(find $O/s_$tag -name '*kernel_stats.csv' | head -1) $O/kernel_stats_$tag.csv
   gzip -c $(find $O/s_$tag -name '*kernel_trace.csv' | head -1) > $O/kernel_trace_$tag.csv.gz

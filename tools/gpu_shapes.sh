@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/shapes
 mkdir -p $O
 for K in 7 37 100; do
-  timeout -k 10 200 python bench.py --steps $K --warmup 3 --cpu-seconds 0 --both-layouts 0 > $O/k$K.json 2> $O/k$K.err || { tail -10 $O/k$K.err; exit 1; }
+  timeout -k 10 200 python bench.py --full --steps $K --warmup 3 --cpu-seconds 0 --both-layouts 0 > $O/k$K.json 2> $O/k$K.err || { tail -10 $O/k$K.err; exit 1; }
   grep '^{"metric' $O/k$K.json | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('K=$K', d['config']['layout'], 'E', d['config']['refill_every'], 'H', d['config']['horizon'], '%.3e' % d['value'], d['config']['timed'])"
 done
 bash tools/gpu_dp_rehearsal.sh

@@ -13,7 +13,7 @@ i=0
 files=""
 for C in "$P1" "$P2"; do
   i=$((i+1))
-  timeout -s KILL 240 rocprofv3 --kernel-trace --output-format csv --pmc $C -d $O/p$i -o run -- python3 $R/bench.py ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --both-layouts 0} > $O/p$i.log 2>&1 || { tail -20 $O/p$i.log; exit 1; }
+  timeout -s KILL 240 rocprofv3 --kernel-trace --output-format csv --pmc $C -d $O/p$i -o run -- python3 $R/bench.py --full ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --both-layouts 0} > $O/p$i.log 2>&1 || { tail -20 $O/p$i.log; exit 1; }
   files="$files $O/p$i/run_counter_collection.csv"
 done
 python3 $R/tools/sq_summary.py "${KERNEL:-mgx_rollout_kernel}" $R/gpurun_out/sq_${TAG:-x}.json $files

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/trace_${TAG:-x}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw -o run -- python3 $R/bench.py ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5} > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw -o run -- python3 $R/bench.py --full ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5} > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 F=$(find $O/raw -name '*kernel_trace.csv' | head -1)
 S=$(find $O/raw -name '*kernel_stats.csv' | head -1)
 cp $S $O/kernel_stats.csv
