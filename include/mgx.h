@@ -348,8 +348,13 @@ mgx_status mgx_random_actions(int32_t *out_dev, int64_t count, int n_actions, ui
  * only, no reference counterpart (tools/diag_ring_levels.py: the ring-level distribution over long runs). */
 mgx_status mgx_ring_levels(mgx_handle *h, void *stream, uint16_t *levels);
 
-/* Diagnostics: the first n (<= 32) raw device counters (phase / section clocks of
- * -DMGX_STAMPS / -DMGX_GEN_STAMPS builds; zero otherwise).  Synchronises. */
+/* Diagnostics: the first n (<= 32) raw device counters.  [0..2], in every build, say how the refill used the
+ * prefix records of the MT19937 stream (multi-room problems with the ring; zero otherwise): [0] lookups -- episode
+ * generation attempts the refill started with the records on, since mgx_create; [1] hits -- those whose record
+ * matched, so that the attempt took its MT-only prefix from it instead of drawing it; [2] the record frontier:
+ * every stream word below it has had its record computed (mgx_stats [7] is the words generated, the frontier
+ * follows it by what the last MT slide generated).  [3] unused; [4..31] phase / section clocks of -DMGX_STAMPS /
+ * -DMGX_GEN_STAMPS / -DMGX_REFILL_CLOCK builds (zero otherwise).  Synchronises. */
 mgx_status mgx_debug_counters(mgx_handle *h, void *stream, uint64_t *out, int n);
 
 /* Test/debug: copy env state to HOST buffers (any may be NULL); synchronises.

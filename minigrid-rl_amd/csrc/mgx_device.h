@@ -956,6 +956,56 @@ __host__ __device__ __forceinline__ void pfx_unpack(uint64_t r, Prefix &P) {
         P.dopen |= ((f >> 9) & 1u) << d;
     }
 }
+// ---- what one MT slide launch does to the stream and its records (mgx_mt_slide_kernel; host-callable: the
+// arithmetic is driven over synthetic growth sequences by tests/test_record_frontier_host.py) --------------------
+constexpr int MT_SB_WORDS = 3120;                         // lcm(624, 10): five MT blocks = 312 whole groups
+constexpr int MT_SB_GROUPS = MT_SB_WORDS / MT_FIELDS;
+constexpr int MT_SLIDE_MAX_SB = 64;                       // super-blocks one slide generates at most (200 k words)
+// Super-blocks a launch generates: up to group want_hi, while the ring (ring_groups slots) has room above the oldest
+// live group need_lo.  A launch therefore never generates a whole ring: 2^k mod 312 >= 40 groups for the rings of
+// 2^9 .. 2^14 groups, and larger rings exceed MT_SLIDE_MAX_SB super-blocks -- at least 400 words short of one.
+__host__ __device__ __forceinline__ int mt_slide_superblocks(unsigned long long hi, unsigned long long need_lo,
+                                                             unsigned long long want_hi,
+                                                             unsigned long long ring_groups) {
+    int nsb = 0;
+    while (nsb < MT_SLIDE_MAX_SB && hi + (unsigned long long)nsb * MT_SB_GROUPS < want_hi &&
+           hi + (unsigned long long)(nsb + 1) * MT_SB_GROUPS <= need_lo + ring_groups)
+        nsb++;
+    return nsb;
+}
+// The records a launch computes, from the frontier rec_done (MtCtl) and the groups generated so far, hi: every
+// position from the frontier up to the last one whose record reads generated words only (`look` past it), so the
+// frontier follows the stream by what the launch before generated, whatever that was -- the launch's `threads`
+// stride over [rec_lo, rec_hi), `strides` positions each.  Never below the words the ring still holds (hi * 10 -
+// ring_words: a record computed from a recycled slot would describe a later pass of the stream under this pass's
+// tag).  The frontier can be below that only if a launch generated more than the ring less `look` (none does, above);
+// the positions [rec_done, rec_lo) are then skipped, and those of them whose slots this launch does not rewrite,
+// [zero_lo, rec_lo), are cleared -- the slots of [rec_lo, rec_hi) are all but `look` of the ring's.  Either way
+// every slot then holds a record from the ring length below the new frontier or none, so a lookup in the live
+// window finds its own position's record, the one a pass before it (the tag differs by one) or nothing.
+struct PfxWindow {
+    unsigned long long zero_lo, rec_lo, rec_hi;   // clear [zero_lo, rec_lo), compute [rec_lo, rec_hi)
+    unsigned long long next_done;                 // the frontier after the launch
+    unsigned long long strides;                   // positions per thread
+};
+__host__ __device__ __forceinline__ PfxWindow pfx_window(unsigned long long rec_done, unsigned long long hi,
+                                                         unsigned long long ring_words, unsigned long long threads,
+                                                         unsigned long long look) {
+    const unsigned long long top = hi * (unsigned long long)MT_FIELDS;
+    const unsigned long long held = top > ring_words ? top - ring_words : 0ull;   // the oldest word in the ring
+    PfxWindow w;
+    w.rec_hi = top > look ? top - look : 0ull;
+    w.rec_lo = rec_done > held ? rec_done : held;
+    if (w.rec_hi < w.rec_lo) w.rec_hi = w.rec_lo;          // (nothing to compute yet)
+    w.zero_lo = w.rec_lo;
+    if (rec_done < held) {
+        const unsigned long long kept = w.rec_hi > ring_words ? w.rec_hi - ring_words : 0ull;
+        w.zero_lo = rec_done > kept ? rec_done : kept;
+    }
+    w.next_done = w.rec_hi;
+    w.strides = (w.rec_hi - w.rec_lo + threads - 1) / threads;
+    return w;
+}
 
 template <int NW>
 __device__ __forceinline__ void gen_rooms(Gen<NW> &G, const Prefix &P) {

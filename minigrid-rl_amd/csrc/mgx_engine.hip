@@ -42,7 +42,8 @@ constexpr int BLOCK_ENVS = 64;
 typedef uint16_t rpos_t;                    // episode ring positions (mod 2^16)
 constexpr int MGX_MAX_RING = 4096;          // ring depth bound (a power of two, far below 2^16)
 constexpr uint32_t NO_POP = 0xFFFFFFFFu;    // mgx_rollout_kernel: no pop this step
-constexpr int MGX_NCOUNTERS = 32;          // [0..3] unused (per-workgroup slots), [4..7] step stamps, [8..] generator stamps
+constexpr int MGX_NCOUNTERS = 32;          // [0..2] prefix-record use (filled by the host, mgx_debug_counters), [3] unused,
+                                           // [4..7] step stamps, [8..] generator stamps
 constexpr int BLOCK_THREADS = 256;
 constexpr int FRAME = 147;                 // 3 x 7 x 7
 constexpr int FRAME_DW4 = 147;             // dwords per env row at n_stack == 4 (588 B)
@@ -76,13 +77,15 @@ struct MtCtl {
     // that the ceiling alternates between floor and ceil of the target instead of always rounding up
     unsigned long long round_acc;
     int round_cap, round_pad;
-    // prefix records (KParams.pfx): every stream position below rec_done has one (computed by the slide, a pass behind
-    // the stream's generation: positions are read long after they are generated, MT_AHEAD)
+    // prefix records (KParams.pfx): the frontier -- every stream position below rec_done has had its record computed.
+    // Each slide computes all the records from the frontier up to hi * 10 - PFX_LOOK before it generates (pfx_window,
+    // mgx_device.h), so after every launch the frontier is behind the stream by what that launch generated + PFX_LOOK,
+    // whatever the engine's size (positions are read long after they are generated, MT_AHEAD), and every slot of
+    // the records holds a position from the ring length below the frontier or nothing: the record's 8-bit pass tag
+    // only ever tells a position from the one a single pass before it
     unsigned long long rec_done;
 };
-constexpr int MT_SB_WORDS = 3120;                         // lcm(624, 10): five MT blocks = 312 whole groups
-constexpr int MT_SB_GROUPS = MT_SB_WORDS / MT_FIELDS;
-constexpr int MT_SLIDE_MAX_SB = 64;                       // super-blocks one slide generates at most (200 k words)
+// (MT_SB_WORDS, MT_SB_GROUPS, MT_SLIDE_MAX_SB: mgx_device.h, with the slide's arithmetic)
 constexpr unsigned long long MT_AHEAD = 1ull << 19;       // words kept generated past the furthest producer cursor
 constexpr long long MT_HOST_FILL = 1ll << 20;             // words the host generates at create
 // 256 threads: the slider must find room on a CU beside the step / rollout kernels (a 1,024-thread
@@ -115,7 +118,7 @@ struct KParams {
     uint64_t *mt;                   // packed MT19937(seed) stream: ten 5-bit fields per group, a ring of
                                     // mt_mask+1 groups + MT_PAD mirror groups, extended by mgx_mt_slide_kernel
     const uint8_t *mtok;
-    unsigned long long *counters;   // [0] steps [1] resets [2] livelocks [3] max cursor
+    unsigned long long *counters;   // diagnostic builds' clocks (MGX_NCOUNTERS)
     uint32_t *err;
     uint64_t mt_mask;               // ring slots - 1
     struct MtCtl *mtc;              // ring window + generator state (device)
@@ -1922,7 +1925,6 @@ __global__ __launch_bounds__(256) void mgx_prefix_kernel(KParams p, uint64_t lo,
          pos += (uint64_t)gridDim.x * blockDim.x)
         p.pfx[pfx_index(pos, p.mt_mask)] = pfx_compute(p, pos);
 }
-constexpr int PFX_PER_THREAD = 2;   // records each slide thread computes per launch (4,096 threads at 65,536 envs)
 
 // ============================================================= refill kernel
 // Pre-generates each env's next episodes into its ring until it holds D.
@@ -1942,6 +1944,10 @@ __device__ __forceinline__ void refill_body(const KParams &p) {
     uint8_t *s_scr = smem + ((64 * p.GSL + 15) & ~15);        // [64] windows + objs
     unsigned long long maxcur = 0;
     uint32_t err = 0;
+    // this wave's attempts started with records on, and those whose record matched: in LDS, summed once per round
+    // by lane 0 (the kernel has no register to spare for them)
+    __shared__ unsigned int s_pfx[2];
+    if (tid == 0) s_pfx[0] = s_pfx[1] = 0u;
     // issue priority over co-resident step / rollout waves (MGX_REFILL_PRIO; wave-uniform)
     if (p.refill_prio == 1) __builtin_amdgcn_s_setprio(1);
     else if (p.refill_prio == 2) __builtin_amdgcn_s_setprio(2);
@@ -2020,19 +2026,31 @@ __device__ __forceinline__ void refill_body(const KParams &p) {
         // ATTEMPTS: an abandoned attempt costs the lane one episode of this epoch's production (unless the
         // invariant needs it), not the wave an extra round -- the retry then continues in the next epoch, its
         // count carried in aux.  The rounds are wave-uniform (the record write below needs every lane).
-        while (__ballot(nfree > 0)) {
+        unsigned long long act;
+        while ((act = __ballot(nfree > 0)) != 0) {
 #if MGX_REFILL_CLOCK
             rc_iters += nfree > 0;
 #endif
+            // a record of this lane's position from the stream's current pass; the round's lookups and hits are
+            // counted for the wave (s_pfx)
+            const bool hit = nfree > 0 && p.pfx && (nrec & 0xFFu) &&
+                             ((uint32_t)(nrec >> 8) & 0xFFu) == pfx_tag(G.cur, p.mt_shift);
+            if (p.pfx) {
+                const int nh = __popcll(__ballot(hit));
+                if (tid == 0) {
+                    s_pfx[0] += (unsigned int)__popcll(act);
+                    s_pfx[1] += (unsigned int)nh;
+                }
+            }
             bool wrote = false;
             uint32_t slot = 0;
             if (nfree > 0) {
                 ResetOut R;
                 G.astart = G.cur;
                 G.abort = false;
-                // a record of this position from the stream's current pass: its words are consumed here, gen_multi
-                // takes its draws from it (the prefix never reaches the live-lock cap: <= 255 of llw words)
-                G.phave = p.pfx && (nrec & 0xFFu) && ((uint32_t)(nrec >> 8) & 0xFFu) == pfx_tag(G.cur, p.mt_shift);
+                // the record's words are consumed here, gen_multi takes its draws from it (the prefix never reaches
+                // the live-lock cap: <= 255 of llw words)
+                G.phave = hit;
                 G.prec = nrec;
                 if (G.phave) G.cur += nrec & 0xFFu;
                 mt_sync(G);
@@ -2114,6 +2132,8 @@ __device__ __forceinline__ void refill_body(const KParams &p) {
         ulonglong4 b = p.blk[2 * p.nblk + blockIdx.x];   // (32-env waves: two slots per 64 envs)
         b.w = b.w > maxcur ? b.w : maxcur;
         b.x = (unsigned long long)csum;
+        b.y += (unsigned long long)s_pfx[0];             // prefix-record lookups and hits of this wave, running sums
+        b.z += (unsigned long long)s_pfx[1];             // (mgx_debug_counters [0], [1])
         p.blk[2 * p.nblk + blockIdx.x] = b;
         if (err) atomicOr(p.err, err);
         if (p.clk.slots) clk_record(p.clk, CLK_REFILL, s_t0);   // (one wave per workgroup)
@@ -2259,17 +2279,21 @@ __global__ __launch_bounds__(SLIDE_THREADS) void mgx_mt_slide_kernel(KParams p) 
         }
     }
     // prefix records of the stream positions generated by the slides before this one (round 6): this launch's
-    // threads take PFX_PER_THREAD positions each from rec_done on, up to the last word a record may read
-    unsigned long long rec_lo = 0, rec_hi = 0;
+    // threads stride over all of them, from the frontier up to the last position whose record reads generated
+    // words only (pfx_window: the work follows the stream's growth -- a few hundred words per epoch at 65,536 envs,
+    // less than a position per thread)
+    unsigned long long rec_next = 0;
     if (p.pfx) {
-        rec_lo = c->rec_done;
-        const unsigned long long top = c->hi * (unsigned long long)MT_FIELDS;
-        rec_hi = top > (unsigned long long)PFX_LOOK ? top - PFX_LOOK : 0ull;
         const unsigned long long T = (unsigned long long)gridDim.x * SLIDE_THREADS;
-        for (int k = 0; k < PFX_PER_THREAD; k++) {
-            const unsigned long long pos = rec_lo + (unsigned long long)blockIdx.x * SLIDE_THREADS + tid + k * T;
-            if (pos < rec_hi) p.pfx[pfx_index(pos, p.mt_mask)] = pfx_compute(p, pos);
+        const PfxWindow w = pfx_window(c->rec_done, c->hi, (p.mt_mask + 1) * (unsigned long long)MT_FIELDS, T,
+                                       (unsigned long long)PFX_LOOK);
+        const unsigned long long t0 = (unsigned long long)blockIdx.x * SLIDE_THREADS + tid;
+        for (unsigned long long pos = w.zero_lo + t0; pos < w.rec_lo; pos += T) p.pfx[pfx_index(pos, p.mt_mask)] = 0ull;
+        for (unsigned long long k = 0; k < w.strides; k++) {
+            const unsigned long long pos = w.rec_lo + t0 + k * T;
+            if (pos < w.rec_hi) p.pfx[pfx_index(pos, p.mt_mask)] = pfx_compute(p, pos);
         }
+        rec_next = w.next_done;
     }
     // the refill waves' consumption (mgx_refill_kernel writes it in its workgroup stats): one per 64 envs
     unsigned long long cs = 0;
@@ -2332,19 +2356,13 @@ __global__ __launch_bounds__(SLIDE_THREADS) void mgx_mt_slide_kernel(KParams p) 
             c->round_acc = acc1;
             c->round_cap = r > 1 ? r : 1;
         }
-        if (p.pfx) {                                  // the positions every workgroup covered (rec_lo, hi as read by all)
-            const unsigned long long T = (unsigned long long)gridDim.x * SLIDE_THREADS * PFX_PER_THREAD;
-            c->rec_done = rec_lo + T < rec_hi ? rec_lo + T : (rec_hi > rec_lo ? rec_hi : rec_lo);
-        }
+        if (p.pfx) c->rec_done = rec_next;            // (every workgroup strode over the same window: rec_done, hi as read by all)
         const unsigned long long m = atomicExch(&c->span_min, ~0ull);   // every workgroup's extremes; reset
         const unsigned long long x = atomicExch(&c->span_max, 0ull);
         c->done = 0;
         const unsigned long long cap = p.mt_mask + 1, hi = c->hi, need_lo = m / MT_FIELDS;
         const unsigned long long want_hi = (x + MT_AHEAD) / MT_FIELDS;    // generated this far ahead ...
-        int nsb = 0;                                                      // ... within the ring above need_lo
-        while (nsb < MT_SLIDE_MAX_SB && hi + (unsigned long long)nsb * MT_SB_GROUPS < want_hi &&
-               hi + (unsigned long long)(nsb + 1) * MT_SB_GROUPS <= need_lo + cap)
-            nsb++;
+        const int nsb = mt_slide_superblocks(hi, need_lo, want_hi, cap);  // ... within the ring above need_lo
         s_hi = hi;
         s_nsb = nsb;
     }
@@ -3198,7 +3216,8 @@ mgx_status mgx_create(const mgx_config *cfg, int device, mgx_handle **out) {
     }
     if (MGX_PFX_MEMO && cfg->problem == MGX_PROBLEM_MULTI && D > 0) {
         // prefix records (round 6): one u64 per word of the MT ring (671 MB at the default 2^26-word ring), zeroed (no
-        // record), then the records of the host-generated start of the stream; the slides keep them a pass behind
+        // record), then the records of the host-generated start of the stream; every slide then computes
+        // the records of what the slide before it generated (MtCtl::rec_done)
         const size_t words = (size_t)ring_groups * MT_FIELDS;
         hipError_t e = hipMalloc(&h->allocs[18], words * sizeof(uint64_t));
         if (e != hipSuccess) return bail(fail(MGX_ERR_OOM, "hipMalloc prefix records"));
@@ -3394,6 +3413,21 @@ mgx_status mgx_debug_counters(mgx_handle *h, void *stream, uint64_t *out, int n)
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize(h->side));
     HIP_TRY(hipMemcpy(out, h->kp.counters, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    // [0], [1], [2] (no kernel writes them): the refill waves' prefix-record lookups and hits, summed over their
+    // stats slots, and the record frontier
+    if (n > 0) {
+        std::vector<ulonglong4> b((size_t)4 * h->kp.nblk);
+        HIP_TRY(hipMemcpy(b.data(), h->kp.blk + (size_t)2 * h->kp.nblk, b.size() * sizeof(ulonglong4),
+                          hipMemcpyDeviceToHost));
+        uint64_t look = 0, hit = 0;
+        for (const ulonglong4 &v : b) { look += v.y; hit += v.z; }
+        unsigned long long rd = 0;
+        if (h->kp.pfx)
+            HIP_TRY(hipMemcpy(&rd, (const char *)h->kp.mtc + offsetof(MtCtl, rec_done), sizeof rd, hipMemcpyDeviceToHost));
+        out[0] = look;
+        if (n > 1) out[1] = hit;
+        if (n > 2) out[2] = rd;
+    }
     return MGX_OK;
 }
 
@@ -3805,12 +3839,12 @@ mgx_status mgx_stats(mgx_handle *h, void *stream, uint64_t out[8]) {
     HIP_TRY(hipMemcpy(b.data(), h->kp.blk, b.size() * sizeof(ulonglong4), hipMemcpyDeviceToHost));
     uint64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // blk sections: [0, nblk) step kernel (x steps, y resets), [nblk, 2 nblk) fixup, [2 nblk, 6 nblk)
-    // refill (x: that wave's consumption at its last launch, not a counter); z live-locks and w max MT cursor
-    // in every section
+    // refill (x: that wave's consumption at its last launch, not a counter; y, z: its prefix-record lookups and
+    // hits, mgx_debug_counters); y resets and z live-locks in the first two sections, w max MT cursor in every one
     for (size_t i = 0; i < b.size(); i++) {
         const ulonglong4 &v = b[i];
-        if (i < (size_t)2 * h->kp.nblk) c[0] += v.x;
-        c[1] += v.y; c[2] += v.z; c[3] = v.w > c[3] ? v.w : c[3];
+        if (i < (size_t)2 * h->kp.nblk) { c[0] += v.x; c[1] += v.y; c[2] += v.z; }
+        c[3] = v.w > c[3] ? v.w : c[3];
     }
     if (h->kp.D > 0) {   // episodes queued in the rings: sum of (tail - head) mod 2^16
         std::vector<rpos_t> ht((size_t)2 * h->kp.n);

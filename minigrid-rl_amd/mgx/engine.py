@@ -248,6 +248,18 @@ class MgxEngine:
         _lib.check(self.L.mgx_debug_counters(self.h, self._stream(), out, n), "mgx_debug_counters")
         return [int(v) for v in out]
 
+    def prefix_stats(self):
+        """How the refill uses the prefix records of the MT19937 stream (multi-room problems with the ring; all
+        zero otherwise): lookups (generation attempts started with the records on, since creation), hits (those
+        whose record matched: the prefix was not drawn again), frontier (every stream word below it has had its
+        record computed), generated (stream words generated so far) and ring_words (the words the device ring
+        holds).  Synchronises; measurement only."""
+        c = self.debug_counters(3)
+        cfg = _lib.MgxConfig()
+        _lib.check(self.L.mgx_get_config(self.h, ctypes.byref(cfg)), "mgx_get_config")
+        return dict(lookups=c[0], hits=c[1], frontier=c[2], generated=self.stats()["mt_generated"],
+                    ring_words=int(cfg.mt_table_words))
+
     def dump_state(self):
         import numpy as np
         n, S = self.n, self.size

@@ -987,6 +987,27 @@ EXPORT void orc_reset(orc_vec *v, int64_t base_seed, int64_t index_offset,
     orc_reset_ex(v, 1, base_seed, index_offset, img, dir, mis, livelock);
 }
 
+/* env i's share of orc_step (below) */
+static void step_env(orc_vec *v, int i, int action, uint8_t *img, uint8_t *dir, uint8_t *mis,
+                     double *reward, uint8_t *term, uint8_t *trunc,
+                     uint8_t *r_img, uint8_t *r_dir, uint8_t *r_mis, int32_t *livelock) {
+    env_t *e = &v->e[i];
+    uint8_t im[7][7][3];
+    double r; int tm, tr;
+    env_step(e, action, im, &r, &tm, &tr);
+    emit_obs(e, i, &im[0][0][0], img, dir, mis);
+    if (reward) reward[i] = r;
+    if (term) term[i] = (uint8_t)tm;
+    if (trunc) trunc[i] = (uint8_t)tr;
+    if (livelock) livelock[i] = 0;
+    if (tm || tr) {
+        int nll = env_reset(e, 0, 0);
+        gen_obs(e, im);
+        emit_obs(e, i, &im[0][0][0], r_img, r_dir, r_mis);
+        if (livelock) livelock[i] = nll;
+    }
+}
+
 /* One vectorised step with SubprocVecEnv auto-reset.  Outputs (NULL = skip):
  * img/dir/mis: the obs returned by env.step (the terminal obs when done);
  * r_img/r_dir/r_mis: the obs of the new episode where done; livelock: number
@@ -994,22 +1015,24 @@ EXPORT void orc_reset(orc_vec *v, int64_t base_seed, int64_t index_offset,
 EXPORT void orc_step(orc_vec *v, const int32_t *actions, uint8_t *img, uint8_t *dir, uint8_t *mis,
                      double *reward, uint8_t *term, uint8_t *trunc,
                      uint8_t *r_img, uint8_t *r_dir, uint8_t *r_mis, int32_t *livelock) {
-    for (int i = 0; i < v->n; i++) {
-        env_t *e = &v->e[i];
-        uint8_t im[7][7][3];
-        double r; int tm, tr;
-        env_step(e, actions[i], im, &r, &tm, &tr);
-        emit_obs(e, i, &im[0][0][0], img, dir, mis);
-        if (reward) reward[i] = r;
-        if (term) term[i] = (uint8_t)tm;
-        if (trunc) trunc[i] = (uint8_t)tr;
-        if (livelock) livelock[i] = 0;
-        if (tm || tr) {
-            int nll = env_reset(e, 0, 0);
-            gen_obs(e, im);
-            emit_obs(e, i, &im[0][0][0], r_img, r_dir, r_mis);
-            if (livelock) livelock[i] = nll;
-        }
+    for (int i = 0; i < v->n; i++)
+        step_env(v, i, actions[i], img, dir, mis, reward, term, trunc, r_img, r_dir, r_mis, livelock);
+}
+
+/* T consecutive orc_step calls of envs [first, first + count) over actions[T][n] in one call; the outputs (rows of
+ * the same [n] arrays) are those of the last step alone.  For the long scripted runs of the tests: no per-step
+ * Python round trip, no obs emitted but the last -- and, the envs being independent (no shared state), calls on
+ * disjoint env ranges may run in parallel threads. */
+EXPORT void orc_step_many(orc_vec *v, const int32_t *actions, int64_t T, int first, int count,
+                          uint8_t *img, uint8_t *dir, uint8_t *mis, double *reward, uint8_t *term, uint8_t *trunc,
+                          uint8_t *r_img, uint8_t *r_dir, uint8_t *r_mis, int32_t *livelock) {
+    if (first < 0 || count < 0 || first + count > v->n) return;
+    for (int i = first; i < first + count; i++) {
+        for (int64_t t = 0; t + 1 < T; t++)
+            step_env(v, i, actions[(size_t)t * v->n + i], NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL);
+        if (T > 0)
+            step_env(v, i, actions[(size_t)(T - 1) * v->n + i], img, dir, mis, reward, term, trunc, r_img, r_dir, r_mis,
+                     livelock);
     }
 }
 

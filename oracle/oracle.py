@@ -49,6 +49,7 @@ def lib():
         L.orc_reset.argtypes = [P, ctypes.c_int64, ctypes.c_int64, P, P, P, P]
         L.orc_reset_ex.argtypes = [P, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, P, P, P, P]
         L.orc_step.argtypes = [P] * 12
+        L.orc_step_many.argtypes = [P, P, ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [P] * 10
         L.orc_dump.argtypes = [P] * 10
         L.orc_bench.argtypes = [P, ctypes.c_int64, ctypes.c_uint64]
         L.orc_bench.restype = ctypes.c_int64
@@ -114,6 +115,32 @@ class OracleVec:
         ll = np.zeros(self.n, np.int32)
         self.L.orc_step(self.h, _p(a), _p(img), _p(d), _p(m), _p(rew), _p(term), _p(trunc),
                         _p(rimg), _p(rd), _p(rm), _p(ll))
+        return dict(image=img, dir=d, mission=m, reward=rew, terminated=term, truncated=trunc,
+                    r_image=rimg, r_dir=rd, r_mission=rm, livelock=ll)
+
+    def step_many(self, actions, threads=1):
+        """len(actions) consecutive step() calls over actions int32 [T, n] in one C call (orc_step_many); returns the
+        last step's outputs alone.  threads > 1: the envs, which share no state, are split over that many threads."""
+        a = np.ascontiguousarray(actions, dtype=np.int32)
+        assert a.ndim == 2 and a.shape[1] == self.n and a.shape[0] > 0
+        img, d, m = self._obs_bufs()
+        rimg, rd, rm = self._obs_bufs()
+        rew = np.zeros(self.n, np.float64)
+        term = np.zeros(self.n, np.uint8)
+        trunc = np.zeros(self.n, np.uint8)
+        ll = np.zeros(self.n, np.int32)
+        bufs = [_p(x) for x in (img, d, m, rew, term, trunc, rimg, rd, rm, ll)]
+
+        def part(k):
+            lo, hi = k * self.n // threads, (k + 1) * self.n // threads
+            self.L.orc_step_many(self.h, _p(a), a.shape[0], lo, hi - lo, *bufs)   # (ctypes drops the GIL)
+        threads = max(1, min(int(threads), self.n))
+        if threads == 1:
+            part(0)
+        else:
+            from concurrent.futures import ThreadPoolExecutor
+            with ThreadPoolExecutor(threads) as ex:
+                list(ex.map(part, range(threads)))
         return dict(image=img, dir=d, mission=m, reward=rew, terminated=term, truncated=trunc,
                     r_image=rimg, r_dir=rd, r_mission=rm, livelock=ll)
 

@@ -110,6 +110,21 @@ int run(int problem, int mission, int S, int nobj, int ado, int n_obst, int n, i
 }
 }  // namespace
 
+// The MT slide's arithmetic (mgx_device.h: pfx_window, mt_slide_superblocks) for tests/test_record_frontier_host.py:
+// out = {zero_lo, rec_lo, rec_hi, next_done, strides}; the constants it is driven with.
+extern "C" void hg_pfx_window(uint64_t rec_done, uint64_t hi, uint64_t ring_words, uint64_t threads, uint64_t look,
+                              uint64_t *out) {
+    const PfxWindow w = pfx_window(rec_done, hi, ring_words, threads, look);
+    out[0] = w.zero_lo; out[1] = w.rec_lo; out[2] = w.rec_hi; out[3] = w.next_done; out[4] = w.strides;
+}
+extern "C" int hg_slide_superblocks(uint64_t hi, uint64_t need_lo, uint64_t want_hi, uint64_t ring_groups) {
+    return mt_slide_superblocks(hi, need_lo, want_hi, ring_groups);
+}
+extern "C" int hg_const(int which) {
+    const int c[] = {PFX_LOOK, MT_FIELDS, MT_SB_GROUPS, MT_SLIDE_MAX_SB};
+    return which >= 0 && which < 4 ? c[which] : -1;
+}
+
 extern "C" int hg_run(int problem, int mission, int S, int nobj, int ado, int n_obst, int n, int64_t seed,
                       int episodes, uint8_t *grids, uint8_t *agent, uint8_t *target, int64_t *cursor, uint64_t *pcg,
                       int32_t *livelock) {

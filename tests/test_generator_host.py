@@ -27,6 +27,9 @@ def _lib():
     L = ctypes.CDLL(LIB)
     P = ctypes.c_void_p
     L.hg_run.argtypes = [ctypes.c_int] * 7 + [ctypes.c_int64, ctypes.c_int] + [P] * 6
+    L.hg_pfx_window.argtypes = [ctypes.c_uint64] * 5 + [P]          # (tests/test_record_frontier_host.py)
+    L.hg_pfx_window.restype = None
+    L.hg_slide_superblocks.argtypes = [ctypes.c_uint64] * 4
     return L
 
 

@@ -634,8 +634,10 @@ def test_mt_stream_outlives_its_ring(ring_depth):
     rng = np.random.default_rng(31)
     acts = torch.as_tensor(rng.integers(0, 7, (T, n)).astype(np.int32), device=eng.device)
     acts_h = acts.cpu().numpy()
+    half = None
     for t in range(T):
         if t == T // 2:
+            half = eng.prefix_stats()
             r = ov.reset(seed=None)
             obs = eng.reset()
             img, dr, mi = EngineSource.newest(obs)
@@ -655,6 +657,16 @@ def test_mt_stream_outlives_its_ring(ring_depth):
     st = eng.stats()
     assert st["mt_generated"] > (2 if ring_depth == 0 else 1) * ring_words, st   # the ring was rewritten
     assert a["mtwords"].max() - a["mtwords"].min() < ring_words
+    if ring_depth == 0:
+        # the refill finds the prefix records of a stream that has wrapped its ring (tests/test_prefix_records.py):
+        # over the second half, reset included, the producers read past the records mgx_create computed (the first
+        # ring length) and the records are the slides'.  A position lacks one only if its prefix takes > 255 words
+        # (at most ~30 randbelow draws, each rejecting with probability <= 1/2: negligible)
+        end = eng.prefix_stats()
+        look, hits = end["lookups"] - half["lookups"], end["hits"] - half["hits"]
+        print("second half: %d hits of %d lookups (%.4f), words generated by the reset %d" %
+              (hits, look, hits / max(look, 1), half["generated"]))
+        assert look > 0 and hits >= 0.99 * look, (half, end)
 
 
 def test_gae_stats_of_overlapping_streams_stay_apart():
