@@ -370,7 +370,11 @@ struct Gen {
 #endif
 #else
 #define GSTAMP(G, k) do { } while (0)
+#ifdef MGX_GCOUNT_HOOK      // host builds only (tools/refill_wave_model.cpp): every loop-iteration site reports its id
+#define GCOUNT(G, k) MGX_GCOUNT_HOOK(k)
+#else
 #define GCOUNT(G, k) do { } while (0)
+#endif
 #endif
 
 // MGX_GEN_SKIP (mgx_diag.h): elimination builds that skip generator sections.
@@ -537,79 +541,91 @@ __device__ __forceinline__ uint64_t randbelow_seq(GT &G, uint64_t prog, int cnt)
     }
     return res;
 }
+// The ten guard bits of a SWAR compare (bit 6 j + 5 of slot j, nothing else set) as a 10-bit mask, bit j = slot j:
+// each 30-bit half gathers with one 32-bit multiply -- slot i's bit at 6 i times the constant's bit at 20 - 5 j
+// lands at 20 + 6 i - 5 j, and 6 i - 5 j is injective for i, j < 5, so no two partial products meet (no carries)
+// and bits 20..24 are the products i = j.  The search loop then runs on 32-bit registers.
+__device__ __forceinline__ uint32_t guard10(uint64_t acc) {
+    constexpr uint32_t K = (1u << 20) | (1u << 15) | (1u << 10) | (1u << 5) | 1u;
+    const uint32_t lo = (uint32_t)acc >> 5, hi = (uint32_t)(acc >> 32) >> 3;
+    return (((lo * K) >> 20) & 31u) | ((((hi * K) >> 20) & 31u) << 5);
+}
 // The reference's rejection loop `while True: x = randint(x0, x1); y = randint(y0, y1);
 // if ok(x, y): break` (two _randbelow per draw) with the rejected cells as a bit set.  One SWAR
 // pass over the next ten words finds every complete draw they hold: x is the first word passing
 // x's test, y the first after it passing y's, the next x the first after that...  so a rejected
-// draw costs a few bit operations instead of two randbelow calls.  A draw that straddles the
-// ten words is taken word by word (randbelow_c).  Word consumption and the live-lock cap are
+// draw costs a few bit operations instead of two randbelow calls.  Word consumption and the live-lock cap are
 // exactly randbelow's: the attempt is abandoned when a draw would need a word past the cap.
 // has_c: the draw is preceded by one more _randbelow (modulus KC: an object placement's
 // random.choice(obj_choice), custom_env.py:662-667 -- no MT word is drawn between the two), decoded from
 // the first pass's words before the cell candidates (round 4: it took a randbelow pass of its own) ->
 // `choice`.
+// The decode is a transducer over the stream's words: [want the choice ->] want x -> want y -> test the cell, a
+// rejected cell back to want x.  Its state (need_c, have_x with the latched x, the rejection count) is carried
+// from one ten-word pass to the next, so a draw that crosses the window's end continues in the next pass: a pass
+// consumes the words through the accepted cell's y, or all ten (the pending draw rejected every word left).
 template <int NW, typename Bad, typename Sat>
 __device__ __forceinline__ void draw_cell(Gen<NW> &G, const RbConst KX, const RbConst KY, int x0, int y0, int &x, int &y,
                                           Bad bad, Sat sat /* probe after SAT_PROBE rejections; null: none */,
                                           bool has_c, const RbConst KC, int &choice) {
     constexpr uint64_t GM = 32ull * MT_REP;              // guard bit of every slot
     int rej = 0;
-    bool need_c = has_c;
+    bool need_c = has_c, have_x = false;
+    uint32_t xv = 0;
 #pragma unroll 1
     for (;;) {
+        GCOUNT(G, 27);
         GCOUNT(G, 21);
         const int o6 = (int)__umul24((uint32_t)G.go, 6u);
         const uint64_t f = ((G.ga >> o6) | (G.gb << (60 - o6))) & MT_LOW60;   // words cur..cur+9
-        uint64_t avail = GM;                             // slots not consumed by an earlier draw
-        int used = 0;                                    // words through the last draw examined
-        if (need_c) {
-            const uint64_t acc = (KC.c1 - f) & GM;
-            if (!acc) {                                  // the choice runs past these ten words
-                const uint32_t left = G.llw - (uint32_t)(G.cur - G.astart);
-                if ((uint32_t)MT_FIELDS > left) {
-                    G.cur = G.astart + G.llw;
-                    G.abort = true;
-                    return;
-                }
-                mt_advance(G, MT_FIELDS);
-                continue;
-            }
-            const int b = __ffsll((long long)acc) - 1;
-            choice = (int)((((uint32_t)(f >> (b - 5))) & 31u) >> KC.sh);
-            avail &= ~((2ull << b) - 1ull);
-            used = (int)((uint32_t)(b + 1) * 171u >> 10);
-            need_c = false;
+        uint32_t avail = 0x3FFu;                         // slots not consumed by an earlier draw
+        if (need_c) {                                    // no accepted word: the choice takes all ten (avail = 0)
+            const uint32_t mc = guard10((KC.c1 - f) & GM);
+            const uint32_t j = (uint32_t)__builtin_ctz(mc | 0x400u);
+            choice = mc ? (int)((((uint32_t)(f >> (6u * j))) & 31u) >> KC.sh) : choice;
+            avail &= ~1u << j;
+            need_c = mc == 0u;
         }
-        const uint64_t accx = (KX.c1 - f) & GM, accy = (KY.c1 - f) & GM;    // slot passes x's / y's test
-        bool ok = false;
+        const uint32_t mx = guard10((KX.c1 - f) & GM), my = guard10((KY.c1 - f) & GM);   // slot passes x's / y's test
+        // one candidate cell per iteration, one exit: the cell is accepted, or x or y runs past these ten words
+        // (slot 10 = none: the shifted masks then empty `avail`)
+        bool ok;
+        uint32_t jy;
 #pragma unroll 1
         for (;;) {
-            const uint64_t cx = accx & avail;
-            if (!cx) break;
-            const int bx = __ffsll((long long)cx) - 1;                   // guard bit 6 jx + 5
-            const uint64_t cy = accy & avail & ~((2ull << bx) - 1ull);
-            if (!cy) break;
-            const int by = __ffsll((long long)cy) - 1;
-            x = x0 + (int)(((uint32_t)(f >> (bx - 5)) & 31u) >> KX.sh);
-            y = y0 + (int)(((uint32_t)(f >> (by - 5)) & 31u) >> KY.sh);
-            used = (int)((uint32_t)(by + 1) * 171u >> 10);               // jy + 1
-            avail &= ~((2ull << by) - 1ull);
-            if (!bad(x, y)) { ok = true; break; }
+            GCOUNT(G, 25);
+            const uint32_t cx = mx & avail;
+            const uint32_t jx = (uint32_t)__builtin_ctz(cx | 0x400u);
+            const uint32_t xn = (((uint32_t)(f >> (6u * jx))) & 31u) >> KX.sh;
+            const uint32_t av = have_x ? avail : avail & (~1u << jx);
+            xv = have_x ? xv : xn;
+            const uint32_t cy = my & av;
+            jy = (uint32_t)__builtin_ctz(cy | 0x400u);
+            x = x0 + (int)xv;
+            y = y0 + (int)((((uint32_t)(f >> (6u * jy))) & 31u) >> KY.sh);
+            avail = av & (~1u << jy);
+            have_x = cy == 0u && (have_x || cx != 0u);   // an x without its y stays latched
+            ok = cy != 0u && !bad(x, y);
+            if (ok || cy == 0u) break;
             if (++rej == SAT_PROBE && !sat()) { live_lock(G); return; }
         }
+        const int used = ok ? (int)jy + 1 : MT_FIELDS;
         const uint32_t left = G.llw - (uint32_t)(G.cur - G.astart);
         if ((uint32_t)used > left) {                     // a draw would pass the cap
             G.cur = G.astart + G.llw;
             G.abort = true;
             return;
         }
-        mt_advance(G, used);
+        // consume: the group rotation as selects; g + 2 re-read either way (the same group when nothing rotates)
+        G.cur += (uint64_t)used;
+        G.go += used;
+        const bool rot = G.go >= MT_FIELDS;
+        G.go -= rot ? MT_FIELDS : 0;
+        G.ga = rot ? G.gb : G.ga;
+        G.gb = rot ? G.gc : G.gb;
+        G.gi += rot ? 1ull : 0ull;
+        G.gc = win_group(G, G.gi + 2);
         if (ok) return;
-        x = x0 + randbelow_c(G, KX);                     // the draw across the window's end
-        y = y0 + randbelow_c(G, KY);
-        if (G.abort) return;
-        if (!bad(x, y)) return;
-        if (++rej == SAT_PROBE && !sat()) { live_lock(G); return; }
     }
 }
 
@@ -1047,20 +1063,46 @@ __device__ __forceinline__ void gen_rooms(Gen<NW> &G, const Prefix &P) {
         // rejection loop: a lane's draws go to the goal until one is accepted (free, not next to
         // a door), then to the agent (free).  Each lane draws exactly the reference's sequence;
         // the wave no longer waits for its slowest goal before any lane places its agent.
+        // The loop only draws and tests (the wave runs it as often as its slowest lane: ~17 times for a lane
+        // mean of 5.4 at S = 8): the goal's grid store and objs entry follow it, the goal's cell counting as
+        // occupied for the agent's draws meanwhile.
         bool agent = false;
+        int gcell = -1;
+        if constexpr (NW <= 2) {
 #pragma unroll 1
-        for (uint32_t it = 0;; ++it) {
-            GCOUNT(G, 22);
-            if (it > 2 * PCG_LOOP_LIMIT) { G.err |= 4u; G.ax = 1; G.ay = 1; break; }
-            int x, y;
-            pcg_cell(G.pcg, S, x, y);
-            if (occupied(G, y * S + x)) continue;          // (the agent is not placed yet: G.ax = -1)
-            if (agent) { G.ax = x; G.ay = y; break; }
-            if (next2door(G, x, y)) continue;              // goal placed then removed: net no-op
-            gx = x; gy = y;
+            for (uint32_t it = 0;; ++it) {
+                GCOUNT(G, 22);
+                if (it > 2 * PCG_LOOP_LIMIT) { G.err |= 4u; G.ax = 1; G.ay = 1; break; }
+                int x, y;
+                pcg_cell(G.pcg, S, x, y);
+                const int b = y * S + x;
+                Bits<NW> rejm = G.occ;                     // goal: occupied or next to a door; agent: occupied
+                rejm.w0 |= agent ? 0ull : G.dn.w0;
+                if (NW > 1) rejm.w1 |= agent ? 0ull : G.dn.w1;
+                if (rejm.test(b)) continue;
+                if (agent) { G.ax = x; G.ay = y; break; }
+                gx = x; gy = y; gcell = b;
+                G.occ.set(b);                              // (put() below sets it again)
+                agent = true;
+            }
+        } else {
+#pragma unroll 1
+            for (uint32_t it = 0;; ++it) {
+                GCOUNT(G, 22);
+                if (it > 2 * PCG_LOOP_LIMIT) { G.err |= 4u; G.ax = 1; G.ay = 1; break; }
+                int x, y;
+                pcg_cell(G.pcg, S, x, y);
+                const int b = y * S + x;
+                if (occupied(G, b) || b == gcell) continue;    // (the agent is not placed yet: G.ax = -1)
+                if (agent) { G.ax = x; G.ay = y; break; }
+                if (next2door(G, x, y)) continue;              // goal placed then removed: net no-op
+                gx = x; gy = y; gcell = b;
+                agent = true;
+            }
+        }
+        if (gcell >= 0) {
             put(G, gx, gy, CODE_GOAL);
             add_obj(G, T_GOAL, 15, gx, gy);
-            agent = true;
         }
         G.adir = pcg_integers(G.pcg, 0, 4);
     }

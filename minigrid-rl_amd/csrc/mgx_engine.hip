@@ -2101,8 +2101,13 @@ __device__ __forceinline__ void refill_body(const KParams &p) {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
         if (producer) {
-            store_rng(G, p, e, (uint32_t)livelocks);
-            p.ring_tail[e] = tail;                 // published by the slide that follows (ring_pubn)
+            // the env index formed again from the lane id (a producer has tid < EPW): the addresses of the stores
+            // below are then not kept in registers across the rounds (the generator has none to spare: they spilled)
+            int lane = tid;
+            asm volatile("" : "+v"(lane));
+            const int64_t e2 = (int64_t)blockIdx.x * EPW + lane;
+            store_rng(G, p, e2, (uint32_t)livelocks);
+            p.ring_tail[e2] = tail;                // published by the slide that follows (ring_pubn)
             maxcur = G.cur;
             err = G.err;
         }
