@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MGX_ABI_VERSION 7
+#define MGX_ABI_VERSION 8
 
 /* Live-lock cap (engine policy; the reference hangs): a
  * reset attempt may consume at most this many MT19937 words; the attempt that
@@ -238,6 +238,60 @@ mgx_status mgx_gather_ring(const mgx_handle *h, const uint8_t *rows_dev, const u
                            const uint8_t *starts_dev, int64_t n_envs, int64_t ring_rows, const int64_t *index_dev,
                            int64_t n_samples, const uint8_t *terminal_rows_dev, void *image_dev, int image_f32,
                            void *direction_dev, int direction_f32, uint8_t *mission_dev, void *stream);
+
+/* ---- Fused actor-critic inference over compact rows (ABI 8) ------------------------------------
+ * The forward pass of the reference's policy (CustomPPOPolicy with the default `arch`: policy.py
+ * DEFAULT_ARCH, net_arch pi = vf = [64, 64] Tanh, 7 actions) for n_samples (t, env) pairs of a compact
+ * buffer, in ONE launch: what ActorCriticPolicy.forward / predict_values compute on the observation
+ * mgx_gather_ring would build for the same sample -- same slot validity, walk-back, ring wrap and
+ * terminal-row case; empty slots are zeros, image = u8 * (1/255), direction = one-hot of row byte 0 --
+ * without materialising that observation.  fp32 with fp32 accumulation.
+ *
+ * Weight blob (fp32, mgx_policy_blob_words(n_stack) words; K = n_stack): every tensor in its torch
+ * row-major layout, concatenated in this order:
+ *    1. direction Linear        W[16][4K], b[16]
+ *    2. image conv1             W[16][3K][2][2], b[16]
+ *    3. image conv2             W[32][16][2][2], b[32]
+ *    4. image conv3             W[64][32][2][2], b[64]
+ *    5. policy_net L0           W[64][208], b[64]     (features: direction 16 | image 64 | mission 128)
+ *    6. policy_net L1           W[64][64], b[64]
+ *    7. value_net_body L0, L1   as 5 and 6
+ *    8. action_net              W[7][64], b[7]
+ *    9. value_net               W[1][64], b[1]
+ * (46,984 words at K = 4).  The mission GRU does not run on the device: the valid slots of a stack are
+ * contiguous from the newest and share one mission id, so the mission features take only (mission id,
+ * v = number of valid slots) values, and the caller tabulates them with the policy's own Embedding + GRU:
+ * mission_feat[mid][v-1][:] = features of K - v zero frames followed by v copies of mid's 32 tokens. */
+int64_t mgx_policy_blob_words(int n_stack);   /* host only; -1 unless 1 <= n_stack <= 8 */
+
+typedef struct mgx_policy {
+    const float *blob_dev;          /* f32 [mgx_policy_blob_words(n_stack)]; 4-byte aligned */
+    const float *mission_feat_dev;  /* f32 [256][n_stack][128]; 16-byte aligned (read as float4) */
+    int32_t mode;                   /* 0: values (and logits) only, 1: deterministic action, 2: sampled action */
+    int32_t reserved0;              /* 0 */
+    uint64_t seed;                  /* mode 2 */
+    uint64_t *counter_dev;          /* mode 2: u64 [2], the contract of mgx_random_actions' counter_dev */
+} mgx_policy;
+
+typedef struct mgx_act_out {        /* each optional; actions_dev and log_probs_dev required when mode != 0 */
+    int64_t *actions_dev;           /* i64 [n_samples] */
+    float *values_dev;              /* f32 [n_samples]: value_net output */
+    float *log_probs_dev;           /* f32 [n_samples]: l[action] - max l - log(total) */
+    float *logits_dev;              /* f32 [n_samples][7]: action_net output l */
+} mgx_act_out;
+
+/* rows_dev .. terminal_rows_dev: exactly mgx_gather_ring's sample addressing.  Mode 1: action = the first
+ * index of the maximum logit.  Mode 2: u = (h >> 40) * 2^-24 with h = mgx_random_actions' hash of (seed,
+ * counter_dev[0], sample index b); p_a = exp(l_a - max l) accumulated in fp32 in index order (cum_a, total =
+ * cum_6); action = the smallest a with cum_a > u * total, 6 if there is none; the launch then advances
+ * counter_dev[0] by one on the device (a replayed graph draws afresh; launches sharing a counter must not
+ * overlap).  Only enqueues on `stream` (no allocation, no host sync).  MGX_ERR_INVALID before any HIP call
+ * for: null pol / out / blob / feature table, n_samples <= 0, mode outside 0..2, a null counter_dev in
+ * mode 2, missing actions_dev / log_probs_dev when mode != 0, 0 < ring_rows < n_stack. */
+mgx_status mgx_policy_act(const mgx_handle *h, const uint8_t *rows_dev, const uint8_t *mission_ids_dev,
+                          const uint8_t *starts_dev, int64_t n_envs, int64_t ring_rows, const int64_t *index_dev,
+                          int64_t n_samples, const uint8_t *terminal_rows_dev, const mgx_policy *pol,
+                          const mgx_act_out *out, void *stream);
 
 /* Makes `stream` wait for the in-flight refill, if any (no host sync). */
 mgx_status mgx_join(mgx_handle *h, void *stream);

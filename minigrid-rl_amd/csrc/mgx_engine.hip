@@ -2727,6 +2727,8 @@ __global__ __launch_bounds__(256) void mgx_gather_kernel(const uint8_t *__restri
     }
 }
 
+#include "mgx_policy.h"   // mgx_policy_act's kernel (fused actor-critic forward over compact rows)
+
 // ================================================================== host side
 thread_local std::string g_last_error;
 
@@ -3213,6 +3215,14 @@ mgx_status mgx_create(const mgx_config *cfg, int device, mgx_handle **out) {
     MGX_SET_LDS(mgx_scene_kernel, h->lds_refill);
 #undef MGX_SET_LDS
 #undef MGX_SET_LDS1
+    switch (cfg->n_stack) {   // mgx_policy_act: this handle's n_stack only
+#define MGX_POL_LDS(KK) \
+    case KK: HIP_TRY(hipFuncSetAttribute((const void *)mgx_policy_kernel<KK>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                         (int)pol_lds_bytes(KK))); break;
+        MGX_POL_LDS(1) MGX_POL_LDS(2) MGX_POL_LDS(3) MGX_POL_LDS(4) MGX_POL_LDS(5) MGX_POL_LDS(6) MGX_POL_LDS(7) MGX_POL_LDS(8)
+#undef MGX_POL_LDS
+        default: break;
+    }
     {
         hipError_t e = hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming);
@@ -3779,6 +3789,47 @@ mgx_status mgx_random_actions(int32_t *out_dev, int64_t count, int n_actions, ui
     const int64_t blocks = std::min<int64_t>((count + 1023) / 1024, 1024);
     hipLaunchKernelGGL(mgx_random_actions_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out_dev,
                        count, (uint32_t)n_actions, seed, (unsigned long long *)counter_dev);
+    HIP_TRY(hipGetLastError());
+    return MGX_OK;
+}
+
+int64_t mgx_policy_blob_words(int n_stack) {
+    return n_stack >= 1 && n_stack <= 8 ? (int64_t)pol_blob(n_stack).words : -1;
+}
+
+mgx_status mgx_policy_act(const mgx_handle *h, const uint8_t *rows_dev, const uint8_t *mission_ids_dev,
+                          const uint8_t *starts_dev, int64_t n_envs, int64_t ring_rows, const int64_t *index_dev,
+                          int64_t n_samples, const uint8_t *terminal_rows_dev, const mgx_policy *pol,
+                          const mgx_act_out *out, void *stream) {
+    if (!pol || !out) return fail(MGX_ERR_INVALID, "mgx_policy_act: null policy / outputs");
+    if (!pol->blob_dev || !pol->mission_feat_dev) return fail(MGX_ERR_INVALID, "mgx_policy_act: null blob / mission features");
+    if (n_samples <= 0) return fail(MGX_ERR_INVALID, "mgx_policy_act: n_samples must be > 0");
+    if (pol->mode < 0 || pol->mode > 2) return fail(MGX_ERR_INVALID, "mgx_policy_act: mode must be 0, 1 or 2");
+    if (pol->mode == 2 && !pol->counter_dev) return fail(MGX_ERR_INVALID, "mgx_policy_act: mode 2 needs counter_dev");
+    if (pol->mode != 0 && (!out->actions_dev || !out->log_probs_dev))
+        return fail(MGX_ERR_INVALID, "mgx_policy_act: modes 1 and 2 need actions_dev and log_probs_dev");
+    if (!h || !rows_dev || !mission_ids_dev || !starts_dev || !index_dev || n_envs <= 0 || ring_rows < 0)
+        return fail(MGX_ERR_INVALID, "mgx_policy_act: bad sample addressing");
+    const int K = h->kp.n_stack;
+    if (ring_rows > 0 && ring_rows < K) return fail(MGX_ERR_INVALID, "mgx_policy_act: the ring must hold n_stack rows");
+    PolArgs a;
+    a.rows = rows_dev; a.mids = mission_ids_dev; a.starts = starts_dev;
+    a.N = n_envs; a.R = ring_rows; a.index = index_dev; a.B = n_samples; a.newest = terminal_rows_dev;
+    a.blob = pol->blob_dev; a.mfeat = pol->mission_feat_dev; a.mode = pol->mode; a.seed = pol->seed;
+    a.ctr = (unsigned long long *)pol->counter_dev;
+    a.actions = (long long *)out->actions_dev; a.values = out->values_dev; a.log_probs = out->log_probs_dev;
+    a.logits = out->logits_dev;
+    const int64_t nblk = (n_samples + POL_TILE - 1) / POL_TILE;
+#define MGX_POL(KK)                                                                                              \
+    case KK:                                                                                                     \
+        hipLaunchKernelGGL(mgx_policy_kernel<KK>, dim3((unsigned)nblk), dim3(POL_THREADS), pol_lds_bytes(KK),            \
+                           (hipStream_t)stream, a);                                                              \
+        break;
+    switch (K) {
+        MGX_POL(1) MGX_POL(2) MGX_POL(3) MGX_POL(4) MGX_POL(5) MGX_POL(6) MGX_POL(7) MGX_POL(8)
+        default: return fail(MGX_ERR_INVALID, "mgx_policy_act: n_stack out of range");
+    }
+#undef MGX_POL
     HIP_TRY(hipGetLastError());
     return MGX_OK;
 }

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("MGX_LIB_PATH", os.path.join(HERE, "libmgx.so"))   # o
 
 MGX_OK = 0
 GAE_SCRATCH_WORDS = 512  # == MGX_GAE_SCRATCH_WORDS (include/mgx.h)
-ABI_VERSION = 7        # == MGX_ABI_VERSION (include/mgx.h)
+ABI_VERSION = 8        # == MGX_ABI_VERSION (include/mgx.h)
 PROBLEMS = {"multi": 0, "full": 1, "gto": 2, "gtg": 3, "opn": 4, "pkp": 5, "drp": 6, "mov": 7}
 TERMINAL = {"none": 0, "truncated": 1, "all": 2}
 DEVERR = {1: "MT19937 ring: a cursor left the window of the stream the device holds", 2: "action outside 0..6 (ValueError: Unknown action)",
@@ -27,7 +27,8 @@ EXPORTS = ("mgx_last_error", "mgx_abi_version", "mgx_create", "mgx_destroy", "mg
            "mgx_join", "mgx_get_config", "mgx_set_seed", "mgx_gae", "mgx_gae_dones", "mgx_poll_error", "mgx_stats", "mgx_debug_counters", "mgx_dump_state", "mgx_mission_text",
            "mgx_step_compact", "mgx_rollout_compact", "mgx_rollout_compact_gae", "mgx_observe_compact", "mgx_gather",
            "mgx_gather_ring", "mgx_scene", "mgx_set_clock", "mgx_clock_words", "mgx_clock_groups",
-           "mgx_ring_levels", "mgx_random_actions", "mgx_set_random_policy")
+           "mgx_ring_levels", "mgx_random_actions", "mgx_set_random_policy", "mgx_policy_blob_words",
+           "mgx_policy_act")
 CLOCK_CLASSES = 4   # == MGX_CLOCK_CLASSES (include/mgx.h)
 
 
@@ -84,6 +85,20 @@ class MgxGaeArgs(ctypes.Structure):
     ]
 
 
+class MgxPolicy(ctypes.Structure):
+    _fields_ = [
+        ("blob_dev", ctypes.c_void_p), ("mission_feat_dev", ctypes.c_void_p), ("mode", ctypes.c_int32),
+        ("reserved0", ctypes.c_int32), ("seed", ctypes.c_uint64), ("counter_dev", ctypes.c_void_p),
+    ]
+
+
+class MgxActOut(ctypes.Structure):
+    _fields_ = [
+        ("actions_dev", ctypes.c_void_p), ("values_dev", ctypes.c_void_p), ("log_probs_dev", ctypes.c_void_p),
+        ("logits_dev", ctypes.c_void_p),
+    ]
+
+
 class MgxError(RuntimeError):
     pass
 
@@ -126,6 +141,9 @@ def load():
     L.mgx_rollout_compact_gae.argtypes = [P, P, I, ctypes.POINTER(MgxRolloutOut), ctypes.POINTER(MgxGaeArgs), P]
     L.mgx_gather.argtypes = [P, P, P, P, I64, P, I64, P, P, I, P, I, P, P]
     L.mgx_gather_ring.argtypes = [P, P, P, P, I64, I64, P, I64, P, P, I, P, I, P, P]
+    L.mgx_policy_blob_words.argtypes = [I]
+    L.mgx_policy_blob_words.restype = I64
+    L.mgx_policy_act.argtypes = [P, P, P, P, I64, I64, P, I64, P, ctypes.POINTER(MgxPolicy), ctypes.POINTER(MgxActOut), P]
     L.mgx_set_clock.argtypes = [P, P, I, ctypes.POINTER(I)]
     L.mgx_clock_words.argtypes = [P, I]
     L.mgx_clock_words.restype = I64

@@ -33,9 +33,12 @@ def _act_fn(model, deterministic):
 
 @torch.no_grad()
 def evaluate_policy(model, engine, n_eval_episodes=10, deterministic=True, return_episode_rewards=False,
-                    reward_threshold=None):
+                    reward_threshold=None, fused=None):
     """SB3 `evaluate_policy` over `engine` (an MgxEngine).  `model` is an
-    ActorCriticPolicy (its predict(obs, deterministic)) or a callable obs -> actions."""
+    ActorCriticPolicy (its predict(obs, deterministic)) or a callable obs -> actions.
+    fused: a FusedActor of (model, engine) -- the same loop over a small ring CompactBuffer: per step one
+    mgx_policy_act on the compact rows and one mgx_step_compact, no stacked observation (a callable `model`
+    still gets the stacked observation, gathered from the rows)."""
     act = _act_fn(model, deterministic)
     n, dev = engine.n, engine.device
     idx = torch.arange(n, device=dev)
@@ -46,11 +49,30 @@ def evaluate_policy(model, engine, n_eval_episodes=10, deterministic=True, retur
     lens = torch.zeros((n, cap), dtype=torch.int64, device=dev)
     when = torch.full((n, cap), -1, dtype=torch.int64, device=dev)
     obs = engine.reset()
+    if fused is not None:
+        if fused.engine is not engine:
+            raise ValueError("the FusedActor belongs to another engine")
+        from .compact import CompactBuffer
+        buf, bt = CompactBuffer(engine, max(2, engine.n_stack), ring=True), 0
+        buf.observe(0)
     t = 0
     while bool((counts < targets).any()):
-        actions = act(obs)
-        obs = engine.step(actions)
-        rec = engine.done & (counts < targets)
+        if fused is None:
+            actions = act(obs)
+            obs = engine.step(actions)
+            done = engine.done
+        else:
+            if hasattr(model, "predict"):
+                actions = fused.act(buf, bt, deterministic=deterministic)[0]
+            else:
+                actions = model(buf.gather_step(bt, f32=False))
+            buf.step(bt, actions)
+            done = buf.dones[bt].bool()
+            bt += 1
+            if bt == buf.T:                              # next block of the ring (no rows move)
+                buf.carry_over()
+                bt = 0
+        rec = done & (counts < targets)
         slot = counts.clamp(max=cap - 1)
         r = engine.reward64 if engine.reward64 is not None else engine.ep_return.double()
         # only the final step of an episode can pay (PlaygroundEnv.step), so the Monitor sum

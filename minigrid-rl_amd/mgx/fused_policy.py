@@ -1,0 +1,212 @@
+"""Fused actor-critic inference over compact rows (mgx_policy_act, include/mgx.h ABI 8).
+
+`pol(obs)` in the rollout loop is a gather that expands every env's 150-byte observation into the
+stacked fp32 tensor, a chain of library launches for a 47k-parameter net and a Categorical sample.
+FusedActor replaces that line (and predict_values for the bootstrap / last-values passes) with ONE
+HIP kernel that reads the compact rows in place and writes actions, values and log-probs: the
+stacked observation is never built and nothing leaves the device.
+
+Only the reference's own architecture is supported (policy.py DEFAULT_ARCH, net_arch 64/64 Tanh,
+7 actions); anything else raises ValueError.  The kernel does not run the mission GRU: a stack's
+valid slots are contiguous from the newest and share one mission id, so the mission features take
+only (mission id, v = number of valid slots) values -- sync() tabulates them with the policy's own
+Embedding + GRU (<= 256 * n_stack rows) next to the packed weights.  Call sync() after every
+optimiser phase.
+
+Sampling has its own documented stream (include/mgx.h): it is not torch's Categorical stream.
+"""
+import ctypes
+
+import torch
+from torch import nn
+
+from . import _lib
+from .policy import DEFAULT_ARCH, OBS_KEYS
+
+N_ACTIONS = 7
+FEATURES = 208            # direction 16 | image 64 | mission 128
+
+
+def blob_layout(n_stack):
+    """[(name, shape)] of the packed weight blob, in include/mgx.h's order."""
+    k = int(n_stack)
+    lay = [("direction.weight", (16, 4 * k)), ("direction.bias", (16,)),
+           ("conv1.weight", (16, 3 * k, 2, 2)), ("conv1.bias", (16,)),
+           ("conv2.weight", (32, 16, 2, 2)), ("conv2.bias", (32,)),
+           ("conv3.weight", (64, 32, 2, 2)), ("conv3.bias", (64,))]
+    for net in ("policy_net", "value_net_body"):
+        lay += [(net + ".0.weight", (64, FEATURES)), (net + ".0.bias", (64,)),
+                (net + ".1.weight", (64, 64)), (net + ".1.bias", (64,))]
+    lay += [("action_net.weight", (N_ACTIONS, 64)), ("action_net.bias", (N_ACTIONS,)),
+            ("value_net.weight", (1, 64)), ("value_net.bias", (1,))]
+    return lay
+
+
+def blob_offsets(n_stack):
+    """{name: (offset, shape)} in fp32 words."""
+    out, o = {}, 0
+    for name, shape in blob_layout(n_stack):
+        n = 1
+        for s in shape:
+            n *= s
+        out[name] = (o, shape)
+        o += n
+    return out
+
+
+def blob_words(n_stack):
+    return sum(int(torch.Size(shape).numel()) for _, shape in blob_layout(n_stack))
+
+
+def _bad(msg):
+    raise ValueError("FusedActor supports only the reference architecture (policy.py DEFAULT_ARCH, net_arch "
+                     "64/64 Tanh, %d actions): %s" % (N_ACTIONS, msg))
+
+
+def _params(policy):
+    """The policy's parameter tensors in blob order; ValueError for any other architecture."""
+    fe = getattr(policy, "features_extractor", None)
+    if fe is None or not hasattr(fe, "extractors"):
+        _bad("no CustomExtractor")
+    k = int(fe.n_frames_stack)
+    if not 1 <= k <= 8:
+        _bad("n_stack %d outside 1..8" % k)
+    if tuple(fe.extractors.keys()) != OBS_KEYS:
+        _bad("extractor keys %s" % (tuple(fe.extractors.keys()),))
+    for key in OBS_KEYS:
+        names = [type(m).__name__.replace("Conv2dGemm", "Conv2d") for m in fe.extractors[key]]
+        if names != [n for n, _ in DEFAULT_ARCH[key]]:
+            _bad("%s extractor is %s" % (key, names))
+    img = [m for m in fe.extractors["image"] if isinstance(m, nn.Conv2d)]
+    for c in img:
+        if tuple(c.kernel_size) != (2, 2) or tuple(c.stride) != (1, 1) or any(c.padding) or \
+                tuple(c.dilation) != (1, 1) or c.groups != 1 or c.bias is None:
+            _bad("conv %s" % (c,))
+    pool = [m for m in fe.extractors["image"] if isinstance(m, nn.MaxPool2d)][0]
+    if pool.kernel_size not in (2, (2, 2)) or pool.stride not in (2, (2, 2)) or pool.padding not in (0, (0, 0)):
+        _bad("pool %s" % (pool,))
+    gru = fe.extractors["mission"][1]
+    if gru.hidden_size != 128 or gru.num_layers != 1 or gru.bidirectional or not gru.batch_first:
+        _bad("mission GRU %s" % (gru,))
+    mods = [fe.extractors["direction"][0]] + img
+    for net in (policy.policy_net, policy.value_net_body):
+        kinds = [type(m) for m in net]
+        if kinds != [nn.Linear, nn.Tanh, nn.Linear, nn.Tanh]:
+            _bad("net_arch %s" % ([m.__name__ for m in kinds],))
+        mods += [net[0], net[2]]
+    mods += [policy.action_net, policy.value_net]
+    tensors = []
+    for m in mods:
+        if m.bias is None:
+            _bad("%s has no bias" % (m,))
+        tensors += [m.weight, m.bias]
+    for t, (name, shape) in zip(tensors, blob_layout(k)):
+        if tuple(t.shape) != shape:
+            _bad("%s is %s, not %s" % (name, tuple(t.shape), shape))
+    return k, tensors
+
+
+def pack_blob(policy):
+    """f32 [mgx_policy_blob_words(n_stack)]: the policy's parameters in include/mgx.h's order."""
+    _, tensors = _params(policy)
+    return torch.cat([t.detach().to(torch.float32).reshape(-1) for t in tensors])
+
+
+def mission_token_stacks(n_stack, tokens=None):
+    """i64 [256, n_stack, 32 * n_stack]: entry [mid, v - 1] is the stacked mission input of a stack with v
+    valid slots: n_stack - v zero frames, then v copies of mission mid's 32 tokens."""
+    k = int(n_stack)
+    tok = torch.as_tensor(_lib.mission_tokens() if tokens is None else tokens).to(torch.int64)   # [256, 32]
+    out = torch.zeros((256, k, k, 32), dtype=torch.int64)
+    for v in range(1, k + 1):
+        out[:, v - 1, k - v:, :] = tok[:, None, :]
+    return out.reshape(256, k, 32 * k)
+
+
+@torch.no_grad()
+def mission_table(policy, tokens=None):
+    """f32 [256, n_stack, 128]: the policy's own Embedding + GRU on every (mission id, v) token stack."""
+    k, _ = _params(policy)
+    fe = policy.features_extractor
+    dev = next(policy.parameters()).device
+    st = mission_token_stacks(k, tokens).reshape(256 * k, 32 * k).to(dev)
+    out = fe._mission_chunked(fe.extractors["mission"], st)
+    return out.to(torch.float32).reshape(256, k, 128).contiguous()
+
+
+class FusedActor:
+    """actions / values / log-probs of `policy` for observations of a CompactBuffer of `engine`, one launch each."""
+
+    def __init__(self, policy, engine, seed=0):
+        k, _ = _params(policy)                       # ValueError before anything touches the device
+        if engine is None or k != engine.n_stack:
+            raise ValueError("policy n_stack %d does not match the engine's" % k)
+        self.policy, self.engine = policy, engine
+        self.K = k
+        self.seed = int(seed) & (2 ** 64 - 1)
+        dev = engine.device
+        words = int(engine.L.mgx_policy_blob_words(k))
+        if words != blob_words(k):
+            raise _lib.MgxError("blob layout mismatch: library %d words, packer %d" % (words, blob_words(k)))
+        self.blob = torch.zeros(words, dtype=torch.float32, device=dev)
+        self.mission_feat = torch.zeros((256, k, 128), dtype=torch.float32, device=dev)
+        self.counter = torch.zeros(2, dtype=torch.int64, device=dev)      # u64 [2] (mgx_random_actions' contract)
+        self._tokens = _lib.mission_tokens()
+        self._pol = _lib.MgxPolicy()
+        self._out = _lib.MgxActOut()
+        self.sync()
+
+    @torch.no_grad()
+    def sync(self):
+        """Repack the blob and rebuild the mission-feature table from the policy's current parameters."""
+        was = self.policy.training
+        self.policy.train(False)
+        self.blob.copy_(pack_blob(self.policy))
+        self.mission_feat.copy_(mission_table(self.policy, self._tokens))
+        self.policy.train(was)
+
+    def _run(self, buf, index, mode, terminal=False, logits=False):
+        e = self.engine
+        if buf.engine is not e:
+            raise ValueError("the buffer belongs to another engine")
+        idx = index.to(torch.int64).contiguous()
+        n = idx.numel()
+        f32 = dict(dtype=torch.float32, device=e.device)
+        values = torch.empty(n, **f32)
+        actions = torch.empty(n, dtype=torch.int64, device=e.device) if mode else None
+        log_probs = torch.empty(n, **f32) if mode else None
+        lg = torch.empty((n, N_ACTIONS), **f32) if logits else None
+        if n == 0:
+            return actions, values, log_probs, lg
+        p, o = self._pol, self._out
+        p.blob_dev, p.mission_feat_dev = self.blob.data_ptr(), self.mission_feat.data_ptr()
+        p.mode, p.seed, p.counter_dev = int(mode), self.seed, self.counter.data_ptr()
+        o.actions_dev = None if actions is None else actions.data_ptr()
+        o.values_dev = values.data_ptr()
+        o.log_probs_dev = None if log_probs is None else log_probs.data_ptr()
+        o.logits_dev = None if lg is None else lg.data_ptr()
+        P = ctypes.c_void_p
+        _lib.check(e.L.mgx_policy_act(e.h, P(buf.rows.data_ptr()), P(buf.mids.data_ptr()), P(buf.starts.data_ptr()),
+                                      buf.N, buf.R if buf.ring else 0, P(idx.data_ptr()), n,
+                                      P(buf.terminal_rows.data_ptr()) if terminal else None,
+                                      ctypes.byref(p), ctypes.byref(o), e._stream()), "mgx_policy_act")
+        return actions, values, log_probs, lg
+
+    def _index(self, buf, t, envs):
+        return buf.index(t, buf._arange if envs is None else envs.to(torch.int64))
+
+    def act(self, buf, t, deterministic=False, envs=None, logits=False):
+        """(actions i64 [N], values f32 [N], log_probs f32 [N]) for observation t of `buf` -- what
+        policy.forward(buf.gather_step(t), deterministic) returns, sampling aside (own stream).
+        logits=True appends the action_net output f32 [N, 7]."""
+        a, v, lp, lg = self._run(buf, self._index(buf, t, envs), 1 if deterministic else 2, logits=logits)
+        return (a, v, lp, lg) if logits else (a, v, lp)
+
+    def values(self, buf, t, terminal=False, envs=None):
+        """policy.predict_values(buf.gather_step(t, terminal=terminal, envs=envs))."""
+        return self._run(buf, self._index(buf, t, envs), 0, terminal=terminal)[1]
+
+    def logits(self, buf, t, terminal=False, envs=None):
+        """(logits f32 [N, 7], values f32 [N]) of observation t (tests)."""
+        _, v, _, lg = self._run(buf, self._index(buf, t, envs), 0, terminal=terminal, logits=True)
+        return lg, v

@@ -64,6 +64,8 @@ class PPOConfig:
     adv_norm: str = "minibatch"         # "minibatch" (reference) | "global" (all-reduced stats)
     mission_cache: bool = True          # policy.py: GRU once per distinct mission stack
     layout: str = "compact"             # rollout storage: "compact" (mgx/compact.py) | "sb3" (stacked obs)
+    fused_act: bool = False             # compact layout: act / bootstrap / last values through mgx_policy_act
+                                        # (mgx/fused_policy.py; own sampling stream) instead of pol(gathered obs)
     env: dict = field(default_factory=lambda: dict(problem="multi", mission=2, size=8, num_objects=4))
 
 
@@ -230,6 +232,10 @@ class CompactRolloutCollector:
         self.ep_returns, self.ep_lens = [], []
         self.stopped = False
         self._n_rollouts = 0
+        self.fused = None
+        if getattr(cfg, "fused_act", False):
+            from .fused_policy import FusedActor
+            self.fused = FusedActor(policy, engine, seed=cfg.seed)
         n, k, dev = engine.n, engine.n_stack, engine.device
         self._obs = dict(image=torch.empty((n, 3 * k, 7, 7), dtype=torch.float32, device=dev),
                          direction=torch.empty((n, 4 * k), dtype=torch.float32, device=dev),
@@ -243,7 +249,9 @@ class CompactRolloutCollector:
     @torch.no_grad()
     def collect(self, callback=None):
         e, pol, cfg, ro = self.engine, self.policy, self.cfg, self.rollout
-        buf = ro.buf
+        buf, fused = ro.buf, self.fused
+        if fused is not None:
+            fused.sync()                   # the optimiser phase since the last rollout changed the weights
         if self._n_rollouts:
             buf.carry_over()
         self._n_rollouts += 1
@@ -251,13 +259,19 @@ class CompactRolloutCollector:
         gamma32 = torch.tensor(cfg.gamma, dtype=torch.float32)
         ep_r, ep_l = [], []
         for t in range(cfg.horizon):
-            obs = buf.gather_step(t, f32=True, out=self._obs)
-            actions, values, log_probs = pol(obs)
+            if fused is not None:
+                actions, values, log_probs = fused.act(buf, t)
+            else:
+                obs = buf.gather_step(t, f32=True, out=self._obs)
+                actions, values, log_probs = pol(obs)
             buf.step(t, actions)
             self.num_timesteps += e.n
             boot = (buf.truncated[t].bool() & ~buf.terminated[t].bool()).nonzero().flatten()
             if boot.numel():
-                tv = pol.predict_values(buf.gather_step(t, terminal=True, envs=boot))
+                if fused is not None:
+                    tv = fused.values(buf, t, terminal=True, envs=boot)
+                else:
+                    tv = pol.predict_values(buf.gather_step(t, terminal=True, envs=boot))
                 r = buf.rewards[t]
                 r.index_put_((boot,), r.index_select(0, boot) + gamma32.to(tv.device) * tv)
             ro.actions[t].copy_(actions)
@@ -271,7 +285,10 @@ class CompactRolloutCollector:
                     self.stopped = True
                     return None
                 pol.train(False)
-        last_values = pol.predict_values(buf.gather_step(cfg.horizon, f32=True, out=self._obs))
+        if fused is not None:
+            last_values = fused.values(buf, cfg.horizon)
+        else:
+            last_values = pol.predict_values(buf.gather_step(cfg.horizon, f32=True, out=self._obs))
         ro.compute_returns_and_advantage(last_values, cfg.gamma, cfg.gae_lambda)
         r, l = torch.stack(ep_r), torch.stack(ep_l)
         m = ~torch.isnan(r)
