@@ -50,7 +50,7 @@ def test_invalid_configs_rejected_without_gpu(lib):
     from mgx import _lib
     P = _lib.PROBLEMS
     bad = [dict(problem=99), dict(size=3), dict(n_envs=0), dict(obstacles=1, percent_obstacles=1.5),
-           dict(mission=3), dict(num_objects=19), dict(n_stack=0),
+           dict(mission=3), dict(num_objects=19), dict(n_stack=0), dict(n_stack=9),
            # room too small for everything place_obj must place: the reference never returns
            dict(problem=P["full"], size=7), dict(problem=P["gtg"], size=5, num_objects=8),
            dict(problem=P["mov"], size=5, num_objects=7, obstacles=1, percent_obstacles=0.3),

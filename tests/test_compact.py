@@ -21,7 +21,10 @@ CASES = [dict(problem="multi", mission=5, size=8, n=4000, n_stack=4),      # BAS
          dict(problem="multi", mission=None, size=8, n=200, n_stack=4),
          dict(problem="multi", mission=1, size=16, n=130, n_stack=4, see_through_walls=False),
          dict(problem="multi", mission=2, size=11, n=77, n_stack=3, all_doors_open=True),
-         dict(problem="pkp", mission=None, size=8, n=64, n_stack=1)]
+         dict(problem="pkp", mission=None, size=8, n=64, n_stack=1),
+         # n_stack 5 and 8: mgx_gather_kernel<5|8>, up to 128 (sample, slot) pairs per tile, a 7-row walk-back
+         dict(problem="multi", mission=None, size=8, n=130, n_stack=8),
+         dict(problem="multi", mission=2, size=8, n=77, n_stack=5)]
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "%s_%s_s%d_n%d_k%d" % (
@@ -76,38 +79,52 @@ def test_gathered_stacks_equal_materialised_stacks(case):
         assert np.array_equal(a_[key], b_[key]), key
 
 
-@pytest.mark.parametrize("ring,T,rolls", [(False, 8, 2), (True, 8, 4), (True, 2, 7), (True, 3, 5)],
-                         ids=["copy_T8", "ring_T8", "ring_T2", "ring_T3"])
-def test_carry_over_and_minibatch_gather(ring, T, rolls):
+@pytest.mark.parametrize("ring,T,rolls,n_stack", [(False, 8, 2, 4), (True, 8, 4, 4), (True, 2, 7, 4), (True, 3, 5, 4),
+                                                  (True, 2, 10, 8), (True, 3, 7, 8), (True, 2, 8, 5), (False, 8, 3, 8)],
+                         ids=["copy_T8", "ring_T8", "ring_T2", "ring_T3", "ring_T2_k8", "ring_T3_k8", "ring_T2_k5",
+                              "copy_T8_k8"])
+def test_carry_over_and_minibatch_gather(ring, T, rolls, n_stack):
     """Rollouts of T steps with the buffer carried over: any (t, env) sample of every rollout after the
     first, in a random minibatch order, gathers the stack the SB3 engine showed at that step (the history
     rows bridge the rollout boundary).  ring=True (the bench's and the collector's layout): the history rows
     are read in place through mgx_gather_ring, the ring wraps several times (T = 2 and 3 < n_stack: the
-    history reaches two blocks back), and the terminal stacks of the finished episodes are checked too."""
+    history reaches two blocks back; at n_stack 8 and 5 it reaches up to four blocks back, the ring being
+    5, 4 and 4 blocks), and the terminal stacks of the finished episodes are checked too.  A condition of the
+    test: among the gathered samples, an episode start lies at every walk-back distance 1..n_stack-1."""
     _need_gpu()
     from mgx import MgxEngine
     from mgx.compact import CompactBuffer
-    n = 96
-    ref = MgxEngine(problem="multi", mission=None, size=8, n_envs=n, mission_dtype=torch.uint8, terminal_mode="all")
-    cmp_ = MgxEngine(problem="multi", mission=None, size=8, n_envs=n, mission_dtype=torch.uint8, terminal_mode="all")
+    n, K = 96, n_stack
+    kw = dict(problem="multi", mission=None, size=8, n_envs=n, n_stack=K, mission_dtype=torch.uint8, terminal_mode="all")
+    ref = MgxEngine(**kw)
+    cmp_ = MgxEngine(**kw)
     buf = CompactBuffer(cmp_, T, ring=ring)
+    if ring:
+        assert buf.blocks == 1 + -(-K // T)
     ref.reset()
     cmp_.reset()
     buf.observe(0)
     g = torch.Generator(device="cuda")
     g.manual_seed(3)
+    age = np.zeros(n, np.int64)                  # steps since the episode's first observation, from the stored starts
+    at_distance = np.zeros(K, np.int64)          # gathered samples whose nearest episode start lies d rows back
+    gs = 0
     for roll in range(rolls):
         if roll:
             buf.carry_over()
         seen = []
         for t in range(T):
             seen.append({k: v.clone() for k, v in ref.obs.items()})
+            if roll:
+                at_distance += np.bincount(np.minimum(age, K), minlength=K + 1)[:K]
             a = torch.randint(0, 7, (n,), device="cuda", generator=g)
-            if t % 5 == 4:
+            if gs % 5 == 4:
                 a[: n // 3] = 6                                  # bursts of 'done'
+            gs += 1
             ref.step(a)
             buf.step(t, a)
             assert torch.equal(buf.dones[t].bool(), ref.done), (roll, t)
+            age = np.where(buf.starts[buf.row(t + 1)].cpu().numpy() != 0, 0, age + 1)
             d = ref.done.nonzero().flatten()
             if d.numel():
                 gt = buf.gather_step(t, terminal=True, f32=False, envs=d)
@@ -121,6 +138,7 @@ def test_carry_over_and_minibatch_gather(ring, T, rolls):
         for key in ("image", "direction", "mission"):
             want = torch.stack([seen[int(tt)][key][int(ee)] for tt, ee in zip(t_.tolist(), env.tolist())])
             assert torch.equal(got[key], want), (roll, key)
+    assert (at_distance[1:] > 0).all(), at_distance
 
 
 def test_graph_replays_equal_eager_steps():
@@ -169,7 +187,9 @@ def test_graph_replays_equal_eager_steps():
 
 
 GATHER_FIXTURES = [("multi_all_s8", 4), ("multi_gtg_s8", 4), ("multi_pkp_s11", 3), ("multi_tgl_s16", 4),
-                   ("novis_multi_all_s8", 2), ("manual_multi_all_s8", 4)]
+                   ("novis_multi_all_s8", 2), ("manual_multi_all_s8", 4),
+                   ("multi_gtg_s8", 5), ("multi_pkp_s11", 6), ("novis_multi_all_s8", 7), ("multi_all_s8", 8),
+                   ("multi_tgl_s16", 8)]
 
 
 @pytest.mark.parametrize("name,n_stack", GATHER_FIXTURES, ids=[f[0] + "_k%d" % f[1] for f in GATHER_FIXTURES])

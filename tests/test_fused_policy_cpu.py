@@ -15,7 +15,7 @@ def lib():
     return _lib.load()
 
 
-@pytest.mark.parametrize("k", [1, 4, 8])
+@pytest.mark.parametrize("k", [1, 4, 5, 6, 7, 8])
 def test_blob_layout(lib, k):
     """mgx_policy_blob_words(K) is the packer's length (46,984 at K = 4) and slicing the blob by the documented
     offsets returns every parameter tensor bit for bit."""
@@ -52,7 +52,7 @@ def test_blob_words_rejects_other_stacks(lib):
         assert int(lib.mgx_policy_blob_words(k)) == -1
 
 
-@pytest.mark.parametrize("k", [1, 3, 4])
+@pytest.mark.parametrize("k", [1, 3, 4, 5, 8])
 def test_mission_table_matches_extractor(lib, k):
     """mission_feat[mid][v-1] = the extractor's mission features of K - v zero frames followed by v copies of
     the mission's tokens, for 'go to goal', an object mission and 'drop', every v."""

@@ -7,7 +7,13 @@ sums of <= 208 terms in different orders: headroom for order, not for another pr
 
 Setup: gtg 6x6, 70 envs (one full 64-sample tile + a 6-lane tail), a ring CompactBuffer of T = 3 (at n_stack 4 the
 walk-back wraps the ring), 40 random-action steps over carried-over rollouts (episodes <= 36 steps, so episode starts
-fall inside stack windows); action_net redrawn N(0, 1) (the initial gain of 0.01 makes every logit nearly tied)."""
+fall inside stack windows); action_net redrawn N(0, 1) (the initial gain of 0.01 makes every logit nearly tied).
+
+n_stack 5..8 (mgx_policy_kernel<5..8>: X = 37 K rows of LDS, 16 direction bits, 15..24 conv1 trips, direction weight
+columns up to 4 K - 1, mission_feat[mid][v-1] with v up to 8): the ring is 3 or 4 blocks of 3 rows and the walk-back
+crosses up to three of them.  The reference observation there is still buf.gather_step, which tests/test_compact.py
+pins to the FrameStackOracle at those depths; at n_stack 8 the run itself also compares the final gathered observation
+with the C oracle's frames stacked by the FrameStackOracle (_oracle_stacks)."""
 import copy
 import ctypes
 
@@ -56,6 +62,28 @@ def _cat(obs_list):
     return {k: torch.cat([o[k] for o in obs_list]) for k in obs_list[0]}
 
 
+def _oracle_stacks(k, actions):
+    """The stacked observation before every step and after the last one: the C oracle stepped with `actions`
+    ([steps, N_ENVS]), its frames stacked by the numpy VecTransposeImage + VecFrameStack restatement."""
+    import oracle as O
+    ov = O.OracleVec(ENV["problem"], ENV["mission"], ENV["size"], ENV["num_objects"], N_ENVS, 42)
+    fs = O.FrameStackOracle(N_ENVS, k)
+
+    def raw(img, dr, mi):
+        return dict(image=O.vec_transpose_image(img), direction=O.one_hot_dir(dr), mission=mi.astype(np.int64))
+
+    r = ov.reset()
+    out = [{kk: v.copy() for kk, v in fs.reset(raw(r["image"], r["dir"], r["mission"])).items()}]
+    for a in actions:
+        o = ov.step(np.asarray(a, dtype=np.int32))
+        done = (o["terminated"] | o["truncated"]).astype(bool)
+        cur = raw(np.where(done[:, None, None, None], o["r_image"], o["image"]), np.where(done, o["r_dir"], o["dir"]),
+                  np.where(done[:, None], o["r_mission"], o["mission"]))
+        st, _ = fs.step(cur, done, raw(o["image"], o["dir"], o["mission"]))
+        out.append({kk: v.copy() for kk, v in st.items()})
+    return out
+
+
 class Run:
     pass
 
@@ -81,7 +109,7 @@ def _run(k):
     r.eng.reset()
     r.buf.observe(0)
     g = torch.Generator().manual_seed(5)
-    obs, lg, val, act, lp, starts = [], [], [], [], [], 0
+    obs, lg, val, act, lp, starts, stepped = [], [], [], [], [], 0, []
     t = 0
     for step in range(STEPS + 1):
         obs.append({kk: v.clone() for kk, v in r.buf.gather_step(t, f32=False).items()})
@@ -91,7 +119,8 @@ def _run(k):
         lg.append(l.double().cpu()); val.append(v.double().cpu()); act.append(a.cpu()); lp.append(p.double().cpu())
         if step == STEPS:
             break
-        r.buf.step(t, torch.randint(0, 7, (N_ENVS,), generator=g).cuda())
+        stepped.append(torch.randint(0, 7, (N_ENVS,), generator=g))
+        r.buf.step(t, stepped[-1].cuda())
         starts += int(r.buf.dones[t].sum())
         t += 1
         if t == T_RING:
@@ -99,6 +128,12 @@ def _run(k):
             t = 0
     r.t = t                                                # the buffer is left at observation t
     r.episode_ends = starts
+    if k == 8:
+        # the reference observation of this file is the gather's: pin it to the oracle here too (the final step, whose
+        # stack was built across carried-over ring blocks)
+        want = _oracle_stacks(k, torch.stack(stepped).numpy())[-1]
+        for kk in ("image", "direction", "mission"):
+            assert np.array_equal(obs[-1][kk].cpu().numpy().astype(np.int64), want[kk].astype(np.int64)), kk
     r.obs = _cat(obs)
     r.logits, r.values, r.actions, r.log_probs = torch.cat(lg), torch.cat(val), torch.cat(act), torch.cat(lp)
     r.ref_logits, r.ref_values = _ref64(r.pol64, r.obs)
@@ -114,7 +149,7 @@ def _run(k):
     return r
 
 
-@pytest.mark.parametrize("k", [1, 2, 3, 4])
+@pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 6, 7, 8])
 def test_forward_parity(k):
     """logits, values and mode-1 log-probs of every sample of every step within 4 x e_torch of the fp64 module."""
     r = _run(k)
@@ -135,7 +170,7 @@ def test_forward_parity(k):
         assert dev[q] <= r.tol[q], (q, dev[q], r.e_torch[q])
 
 
-@pytest.mark.parametrize("k", [1, 3, 4])
+@pytest.mark.parametrize("k", [1, 3, 4, 5, 8])
 def test_deterministic_actions(k):
     """Mode 1 = the fp64 arg-max wherever the fp64 top-2 gap is >= 1e-3; such near-ties are <= 1 % of samples."""
     r = _run(k)
@@ -146,7 +181,7 @@ def test_deterministic_actions(k):
     assert int(r.actions.min()) >= 0 and int(r.actions.max()) <= 6
 
 
-@pytest.mark.parametrize("k", [1, 3, 4])
+@pytest.mark.parametrize("k", [1, 3, 4, 5, 8])
 def test_subsets_and_terminal_rows(k):
     """values(terminal=True, envs=boot) on the steps where truncations occur ('done'-free actions for 36 steps
     force them), and single-env subsets, against the fp64 module on the matching gather_step."""
@@ -212,7 +247,7 @@ def test_splitmix_restatement_matches_random_actions():
     assert out.cpu().tolist() == want
 
 
-@pytest.mark.parametrize("k", [1, 3, 4])
+@pytest.mark.parametrize("k", [1, 3, 4, 5, 8])
 def test_sampling(k):
     """Mode 2: the action is the inverse-cdf choice of the documented u over the kernel's own logits; log-prob =
     log_softmax(logits)[action]; (seed, counter) reproduces; the launch advances the counter."""
@@ -263,29 +298,27 @@ def test_ring_shorter_than_stack_rejected():
     assert st == 1 and b"mgx_policy_act" in e.L.mgx_last_error()
 
 
-def test_collector_fused_act():
-    """PPOConfig(fused_act=True): stored values / log-probs = the fp64 module's evaluate_actions on the stored
-    observations and stored actions (teacher-forced), truncated steps carry gamma * V(terminal), advantages =
-    gae_dones of the stored arrays bit for bit.  'done' is made improbable so that episodes run into the 36-step
-    limit: four rollouts of 12 steps reach it."""
-    r = _run(4)
+def _collector_case(k, horizon, rollouts):
+    """`rollouts` collects of `horizon` steps at n_stack k with PPOConfig(fused_act=True), checked as
+    test_collector_fused_act states; the bounds are _run(k)'s (4 x e_torch at that n_stack)."""
+    r = _run(k)
     from mgx import MgxEngine
     from mgx.engine import gae_dones
     from mgx.ppo import PPOConfig, make_collector
     env = dict(problem="pkp", mission=None, size=6, num_objects=2)
-    cfg = PPOConfig(fused_act=True, n_envs=N_ENVS, horizon=12, n_frames_stack=4, env=env)
-    pol = _policy(4, seed=3).cuda()
+    cfg = PPOConfig(fused_act=True, n_envs=N_ENVS, horizon=horizon, n_frames_stack=k, env=env)
+    pol = _policy(k, seed=3).cuda()
     with torch.no_grad():
         pol.action_net.bias[6] = -30.0
     pol64 = copy.deepcopy(pol).cpu().double()
-    eng = MgxEngine(n_envs=N_ENVS, seed=cfg.seed, n_stack=4, terminal_mode="truncated", mission_dtype=torch.uint8,
+    eng = MgxEngine(n_envs=N_ENVS, seed=cfg.seed, n_stack=k, terminal_mode="truncated", mission_dtype=torch.uint8,
                     reward64=True, **env)
     col = make_collector(eng, pol, cfg)
     assert col.fused is not None
     col.start()
     gamma32 = torch.tensor(cfg.gamma, dtype=torch.float32)
     n_boot = 0
-    for rollout in range(4):
+    for rollout in range(rollouts):
         seen = []
 
         class Cb:
@@ -328,6 +361,21 @@ def test_collector_fused_act():
         assert torch.equal(adv, ro.advantages) and torch.equal(ret, ro.returns)
     assert n_boot > 0, "no truncation exercised"
     eng.poll_error()
+
+
+def test_collector_fused_act():
+    """PPOConfig(fused_act=True): stored values / log-probs = the fp64 module's evaluate_actions on the stored
+    observations and stored actions (teacher-forced), truncated steps carry gamma * V(terminal), advantages =
+    gae_dones of the stored arrays bit for bit.  'done' is made improbable so that episodes run into the 36-step
+    limit: four rollouts of 12 steps reach it."""
+    _collector_case(4, 12, 4)
+
+
+def test_collector_fused_act_stack_deeper_than_horizon():
+    """The same at n_stack 6 with a horizon of 5: every stored observation's stack reaches into the previous
+    rollout's ring block (the ring is 3 blocks of 5 rows), as does every truncation bootstrap's terminal stack.
+    Eight rollouts pass the 36-step limit."""
+    _collector_case(6, 5, 8)
 
 
 def test_evaluate_policy_fused_loop():

@@ -177,7 +177,13 @@ def test_engine_reset_paths_match_fixture(name, ring):
 
 @pytest.mark.parametrize("name,n_stack,mdt", [("multi_all_s8", 4, "i64"), ("multi_pkp_s11", 3, "u8"),
                                               ("multi_tgl_s16", 1, "i64"), ("novis_multi_all_s8", 4, "i64"),
-                                              ("novis_single_gto_s11", 2, "u8")])
+                                              ("novis_single_gto_s11", 2, "u8"),
+                                              # n_stack 5..8: the generic roll with 20..32-B direction rows, a stack
+                                              # that fills for up to 7 steps, 128 mission chunks per env (i64); S = 16
+                                              # at 8 is the largest grid LDS beside the largest stack area
+                                              ("multi_pkp_s11", 5, "i64"), ("novis_single_gto_s11", 5, "u8"),
+                                              ("multi_all_s8", 6, "u8"), ("novis_multi_all_s8", 7, "i64"),
+                                              ("multi_gtg_s8", 8, "u8"), ("multi_tgl_s16", 8, "i64")])
 def test_frame_stack_and_terminal_obs_match_sb3_layer(name, n_stack, mdt):
     """Full stacked observation + stacked terminal_observation every step vs the
     numpy VecTransposeImage/VecFrameStack restatement fed with the fixture."""
@@ -538,18 +544,15 @@ def test_refill_accounting():
     eng.poll_error()
 
 
-@pytest.mark.parametrize("n,terminal_mode", [(77, "all"), (130, "truncated")])
-def test_ragged_block_full_stacks_match_oracle(n, terminal_mode):
-    """A partial last workgroup (n not a multiple of 64, rows not a multiple of 4
-    dwords): full stacked observation and stacked terminal_observation every step,
-    against the C oracle + the numpy VecFrameStack restatement."""
-    _need_gpu()
+def _full_stacks_vs_oracle(n, n_stack, terminal_mode, T=160, **engine_kw):
+    """multi 8x8, n envs, T random steps: the full stacked observation and the stacked terminal_observation of
+    every step against the C oracle + the numpy VecFrameStack restatement."""
     import oracle as O
     from mgx import MgxEngine
-    T = 160
     ov = O.OracleVec("multi", None, 8, 4, n, 42)
-    fs = O.FrameStackOracle(n, 4)
-    eng = MgxEngine(problem="multi", mission=None, size=8, n_envs=n, n_stack=4, terminal_mode=terminal_mode)
+    fs = O.FrameStackOracle(n, n_stack)
+    eng = MgxEngine(problem="multi", mission=None, size=8, n_envs=n, n_stack=n_stack, terminal_mode=terminal_mode,
+                    **engine_kw)
 
     def raw(img, dr, mi):
         return dict(image=O.vec_transpose_image(img), direction=O.one_hot_dir(dr), mission=mi.astype(np.int64))
@@ -579,6 +582,28 @@ def test_ragged_block_full_stacks_match_oracle(n, terminal_mode):
                 assert np.array_equal(got, want_term[k][sel].astype(np.int64)), (t, k)
     assert n_term > 0
     eng.poll_error()
+    return eng
+
+
+@pytest.mark.parametrize("n,n_stack,terminal_mode", [(77, 4, "all"), (130, 4, "truncated"), (77, 5, "all"),
+                                                     (130, 8, "truncated")],
+                         ids=["77-all", "130-truncated", "77-k5-all", "130-k8-truncated"])
+def test_ragged_block_full_stacks_match_oracle(n, n_stack, terminal_mode):
+    """A partial last workgroup (n not a multiple of 64, rows not a multiple of 4
+    dwords): full stacked observation and stacked terminal_observation every step,
+    against the C oracle + the numpy VecFrameStack restatement.  n_stack 5 and 8: the generic roll
+    at depths whose rows leave another dword tail (735 and 1,176 B)."""
+    _need_gpu()
+    _full_stacks_vs_oracle(n, n_stack, terminal_mode)
+
+
+def test_inline_reset_full_stacks_at_n_stack_8():
+    """ring_depth = -1: no episode ring, so finished envs are regenerated inside the step kernel and mgx_reset's
+    kernel is the only other writer of the stacks.  n_stack 8 (the deepest stack the header advertises), a ragged
+    last block: every step's full stacked observation and stacked terminal_observation vs the oracle."""
+    _need_gpu()
+    eng = _full_stacks_vs_oracle(77, 8, "all", T=120, ring_depth=-1)
+    assert eng.ring_depth == 0                       # the engine did run without a ring
 
 
 @pytest.mark.parametrize("ring", [(0, 0, 0), (16, 4, 1), (8, 4, -1)], ids=["default", "d16_k4_cap1", "d8_k4_fill"])

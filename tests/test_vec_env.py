@@ -52,7 +52,8 @@ def _same_obs(a, b):
 
 
 @pytest.mark.parametrize("problem,mission,size,n_stack", [("multi", 5, 8, 4), ("multi", None, 11, 4),
-                                                          ("pkp", 2, 8, 3)])
+                                                          ("pkp", 2, 8, 3),
+                                                          ("multi", None, 8, 8)])   # the deepest stack (int64 missions)
 def test_vec_env_matches_sb3_stack(problem, mission, size, n_stack):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
