@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MGX_ABI_VERSION 8
+#define MGX_ABI_VERSION 9
 
 /* Live-lock cap (engine policy; the reference hangs): a
  * reset attempt may consume at most this many MT19937 words; the attempt that
@@ -292,6 +292,51 @@ mgx_status mgx_policy_act(const mgx_handle *h, const uint8_t *rows_dev, const ui
                           const uint8_t *starts_dev, int64_t n_envs, int64_t ring_rows, const int64_t *index_dev,
                           int64_t n_samples, const uint8_t *terminal_rows_dev, const mgx_policy *pol,
                           const mgx_act_out *out, void *stream);
+
+/* ---- Fused policy gradient over compact rows (ABI 9) ---------------------------------------------
+ * The backward pass of the network above for the same kind of samples, for the PPO update: given the
+ * cotangents of action_net's and value_net's outputs it recomputes the forward pass from the compact rows
+ * and writes
+ *    grad_blob         = sum over samples of d(g_logits . logits + g_values * value) / d blob
+ *    grad_mission_feat = the same derivative with respect to the mission-feature table
+ * (the forward half of a training step is mgx_policy_act in mode 0 with logits_dev set).  The Embedding
+ * and the GRU never run on the device: the caller back-propagates grad_mission_feat through its own
+ * differentiable table.  fp32 with fp32 accumulation; MaxPool's gradient goes to the first maximum in
+ * window order, ReLU's where the pre-activation is positive.
+ *
+ * Summation order.  At most `groups` workgroups run (max_groups, or 256 -- one per CU of an MI355X -- when
+ * it is 0; never more than the ceil(n_samples / 64) tiles).  Workgroup g walks tiles g, g + groups, ...
+ * and adds each tile's weight gradient into its own slab of scratch_dev; a second kernel adds the slabs
+ * in group order.  grad_blob is therefore bitwise reproducible for a given (n_samples, groups).
+ * grad_mission_feat is summed per tile over the samples that share a (mission id, v) row and then added
+ * with fp32 atomics: its summation order across tiles is run-dependent (as torch's index_select backward
+ * is), and rows no sample names stay exactly zero.
+ * scratch_dev needs mgx_policy_grad_scratch_words(n_stack, n_samples, max_groups) words = groups x
+ * mgx_policy_blob_words(n_stack); it is caller-owned and need not be zeroed. */
+int64_t mgx_policy_grad_scratch_words(int n_stack, int64_t n_samples, int max_groups);
+                                    /* host only; -1 unless 1 <= n_stack <= 8, n_samples > 0, max_groups >= 0 */
+
+typedef struct mgx_policy_grad {
+    const float *blob_dev;          /* as mgx_policy */
+    const float *mission_feat_dev;  /* as mgx_policy; only rows some sample names are read (and row 0) */
+    const float *g_logits_dev;      /* f32 [n_samples][7]: dL/d(action_net output) */
+    const float *g_values_dev;      /* f32 [n_samples]:    dL/d(value_net output) */
+    float *grad_blob_dev;           /* f32 [mgx_policy_blob_words(n_stack)], blob order; OVERWRITTEN */
+    float *grad_mission_feat_dev;   /* f32 [256][n_stack][128]; OVERWRITTEN (zero where no sample has that (mid, v)) */
+    float *scratch_dev;             /* f32 [scratch_words], caller-owned, need not be zeroed */
+    int64_t scratch_words;
+    int32_t max_groups;             /* 0: default; else the number of workgroups that share the tiles */
+    int32_t reserved0;              /* 0 */
+} mgx_policy_grad;
+
+/* rows_dev .. index_dev: exactly mgx_policy_act's sample addressing without the terminal-row case.  Only
+ * enqueues on `stream` (the outputs are zeroed on the stream; no allocation, no host sync; capturable).
+ * MGX_ERR_INVALID before any HIP call for: any null pointer, n_samples <= 0, scratch_words below
+ * mgx_policy_grad_scratch_words(...), max_groups < 0, 0 < ring_rows < n_stack. */
+mgx_status mgx_policy_backward(const mgx_handle *h, const uint8_t *rows_dev, const uint8_t *mission_ids_dev,
+                               const uint8_t *starts_dev, int64_t n_envs, int64_t ring_rows,
+                               const int64_t *index_dev, int64_t n_samples, const mgx_policy_grad *g,
+                               void *stream);
 
 /* Makes `stream` wait for the in-flight refill, if any (no host sync). */
 mgx_status mgx_join(mgx_handle *h, void *stream);

@@ -2728,6 +2728,7 @@ __global__ __launch_bounds__(256) void mgx_gather_kernel(const uint8_t *__restri
 }
 
 #include "mgx_policy.h"   // mgx_policy_act's kernel (fused actor-critic forward over compact rows)
+#include "mgx_policy_grad.h"   // mgx_policy_backward's kernels (its gradient)
 
 // ================================================================== host side
 thread_local std::string g_last_error;
@@ -2855,6 +2856,7 @@ struct mgx_handle {
     hipEvent_t ev_fork, ev_done;
     void *allocs[19];       // [17]: mgx_set_random_policy's per-workgroup launch counters, [18] prefix records
     uint32_t *scene_dev;    // mgx_scene's record (inside allocs[15], inline mode only)
+    bool pol_grad_lds;      // mgx_policy_grad_kernel<n_stack> was granted its dynamic LDS (mgx_policy_backward)
 };
 
 extern "C" {
@@ -3223,6 +3225,16 @@ mgx_status mgx_create(const mgx_config *cfg, int device, mgx_handle **out) {
 #undef MGX_POL_LDS
         default: break;
     }
+    h->pol_grad_lds = false;
+    switch (cfg->n_stack) {   // mgx_policy_backward: a refusal here fails that call, not the handle
+#define MGX_PG_LDS(KK) \
+    case KK: h->pol_grad_lds = hipFuncSetAttribute((const void *)mgx_policy_grad_kernel<KK>, \
+                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)pg_lds_bytes()) == hipSuccess; break;
+        MGX_PG_LDS(1) MGX_PG_LDS(2) MGX_PG_LDS(3) MGX_PG_LDS(4) MGX_PG_LDS(5) MGX_PG_LDS(6) MGX_PG_LDS(7) MGX_PG_LDS(8)
+#undef MGX_PG_LDS
+        default: break;
+    }
+    if (!h->pol_grad_lds) (void)hipGetLastError();
     {
         hipError_t e = hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming);
@@ -3830,6 +3842,61 @@ mgx_status mgx_policy_act(const mgx_handle *h, const uint8_t *rows_dev, const ui
         default: return fail(MGX_ERR_INVALID, "mgx_policy_act: n_stack out of range");
     }
 #undef MGX_POL
+    HIP_TRY(hipGetLastError());
+    return MGX_OK;
+}
+
+static int pol_grad_groups(int64_t n_samples, int max_groups) {
+    const int64_t ntiles = (n_samples + POL_TILE - 1) / POL_TILE;
+    return (int)std::min<int64_t>(max_groups > 0 ? max_groups : PG_DEFAULT_GROUPS, ntiles);
+}
+
+int64_t mgx_policy_grad_scratch_words(int n_stack, int64_t n_samples, int max_groups) {
+    if (n_stack < 1 || n_stack > 8 || n_samples <= 0 || max_groups < 0) return -1;
+    return (int64_t)pol_grad_groups(n_samples, max_groups) * pol_blob(n_stack).words;
+}
+
+mgx_status mgx_policy_backward(const mgx_handle *h, const uint8_t *rows_dev, const uint8_t *mission_ids_dev,
+                               const uint8_t *starts_dev, int64_t n_envs, int64_t ring_rows,
+                               const int64_t *index_dev, int64_t n_samples, const mgx_policy_grad *g,
+                               void *stream) {
+    if (!g) return fail(MGX_ERR_INVALID, "mgx_policy_backward: null mgx_policy_grad");
+    if (!g->blob_dev || !g->mission_feat_dev || !g->g_logits_dev || !g->g_values_dev || !g->grad_blob_dev ||
+        !g->grad_mission_feat_dev || !g->scratch_dev)
+        return fail(MGX_ERR_INVALID, "mgx_policy_backward: null device pointer");
+    if (n_samples <= 0) return fail(MGX_ERR_INVALID, "mgx_policy_backward: n_samples must be > 0");
+    if (g->max_groups < 0) return fail(MGX_ERR_INVALID, "mgx_policy_backward: max_groups must be >= 0");
+    if (g->scratch_words <= 0) return fail(MGX_ERR_INVALID, "mgx_policy_backward: scratch_words must be > 0");
+    if (!h || !rows_dev || !mission_ids_dev || !starts_dev || !index_dev || n_envs <= 0 || ring_rows < 0)
+        return fail(MGX_ERR_INVALID, "mgx_policy_backward: bad sample addressing");
+    const int K = h->kp.n_stack;
+    if (K < 1 || K > 8) return fail(MGX_ERR_INVALID, "mgx_policy_backward: n_stack out of range");
+    if (ring_rows > 0 && ring_rows < K)
+        return fail(MGX_ERR_INVALID, "mgx_policy_backward: the ring must hold n_stack rows");
+    if (g->scratch_words < mgx_policy_grad_scratch_words(K, n_samples, g->max_groups))
+        return fail(MGX_ERR_INVALID, "mgx_policy_backward: scratch_words below mgx_policy_grad_scratch_words");
+    if (!h->pol_grad_lds) return fail(MGX_ERR_HIP, "mgx_policy_backward: the device refused the kernel's LDS");
+    PolGradArgs a;
+    a.rows = rows_dev; a.mids = mission_ids_dev; a.starts = starts_dev;
+    a.N = n_envs; a.R = ring_rows; a.index = index_dev; a.B = n_samples;
+    a.blob = g->blob_dev; a.mfeat = g->mission_feat_dev; a.g_logits = g->g_logits_dev; a.g_values = g->g_values_dev;
+    a.gmf = g->grad_mission_feat_dev; a.scratch = g->scratch_dev;
+    a.groups = pol_grad_groups(n_samples, g->max_groups);
+    const int words = pol_blob(K).words;
+    HIP_TRY(hipMemsetAsync(g->grad_mission_feat_dev, 0, (size_t)256 * K * 128 * sizeof(float), (hipStream_t)stream));
+#define MGX_PG(KK)                                                                                               \
+    case KK:                                                                                                     \
+        hipLaunchKernelGGL(mgx_policy_grad_kernel<KK>, dim3((unsigned)a.groups), dim3(POL_THREADS), pg_lds_bytes(), \
+                           (hipStream_t)stream, a);                                                              \
+        break;
+    switch (K) {
+        MGX_PG(1) MGX_PG(2) MGX_PG(3) MGX_PG(4) MGX_PG(5) MGX_PG(6) MGX_PG(7) MGX_PG(8)
+        default: break;
+    }
+#undef MGX_PG
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mgx_policy_fold_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const float *)g->scratch_dev, a.groups, words, g->grad_blob_dev);
     HIP_TRY(hipGetLastError());
     return MGX_OK;
 }

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("MGX_LIB_PATH", os.path.join(HERE, "libmgx.so"))   # o
 
 MGX_OK = 0
 GAE_SCRATCH_WORDS = 512  # == MGX_GAE_SCRATCH_WORDS (include/mgx.h)
-ABI_VERSION = 8        # == MGX_ABI_VERSION (include/mgx.h)
+ABI_VERSION = 9        # == MGX_ABI_VERSION (include/mgx.h)
 PROBLEMS = {"multi": 0, "full": 1, "gto": 2, "gtg": 3, "opn": 4, "pkp": 5, "drp": 6, "mov": 7}
 TERMINAL = {"none": 0, "truncated": 1, "all": 2}
 DEVERR = {1: "MT19937 ring: a cursor left the window of the stream the device holds", 2: "action outside 0..6 (ValueError: Unknown action)",
@@ -28,7 +28,7 @@ EXPORTS = ("mgx_last_error", "mgx_abi_version", "mgx_create", "mgx_destroy", "mg
            "mgx_step_compact", "mgx_rollout_compact", "mgx_rollout_compact_gae", "mgx_observe_compact", "mgx_gather",
            "mgx_gather_ring", "mgx_scene", "mgx_set_clock", "mgx_clock_words", "mgx_clock_groups",
            "mgx_ring_levels", "mgx_random_actions", "mgx_set_random_policy", "mgx_policy_blob_words",
-           "mgx_policy_act")
+           "mgx_policy_act", "mgx_policy_grad_scratch_words", "mgx_policy_backward")
 CLOCK_CLASSES = 4   # == MGX_CLOCK_CLASSES (include/mgx.h)
 
 
@@ -99,6 +99,15 @@ class MgxActOut(ctypes.Structure):
     ]
 
 
+class MgxPolicyGrad(ctypes.Structure):
+    _fields_ = [
+        ("blob_dev", ctypes.c_void_p), ("mission_feat_dev", ctypes.c_void_p), ("g_logits_dev", ctypes.c_void_p),
+        ("g_values_dev", ctypes.c_void_p), ("grad_blob_dev", ctypes.c_void_p),
+        ("grad_mission_feat_dev", ctypes.c_void_p), ("scratch_dev", ctypes.c_void_p),
+        ("scratch_words", ctypes.c_int64), ("max_groups", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+    ]
+
+
 class MgxError(RuntimeError):
     pass
 
@@ -144,6 +153,9 @@ def load():
     L.mgx_policy_blob_words.argtypes = [I]
     L.mgx_policy_blob_words.restype = I64
     L.mgx_policy_act.argtypes = [P, P, P, P, I64, I64, P, I64, P, ctypes.POINTER(MgxPolicy), ctypes.POINTER(MgxActOut), P]
+    L.mgx_policy_grad_scratch_words.argtypes = [I, I64, I]
+    L.mgx_policy_grad_scratch_words.restype = I64
+    L.mgx_policy_backward.argtypes = [P, P, P, P, I64, I64, P, I64, ctypes.POINTER(MgxPolicyGrad), P]
     L.mgx_set_clock.argtypes = [P, P, I, ctypes.POINTER(I)]
     L.mgx_clock_words.argtypes = [P, I]
     L.mgx_clock_words.restype = I64

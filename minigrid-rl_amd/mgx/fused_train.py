@@ -1,0 +1,144 @@
+"""Fused policy gradient for the PPO update (mgx_policy_backward, include/mgx.h ABI 9).
+
+`pol.evaluate_actions(gathered obs, actions)` in Trainer.train expands every sampled observation into
+the stacked fp32 tensor and runs the net as a chain of library launches, forwards and backwards.
+FusedEvaluator replaces that call and its autograd graph: the forward is mgx_policy_act (mode 0, logits)
+on the compact rows in place, the backward is mgx_policy_backward, both inside one
+torch.autograd.Function whose inputs are the packed weight blob and the mission-feature table.  Both
+inputs are built differentiably -- the blob as torch.cat of the parameters in blob_layout order, the
+table by the policy's own Embedding + GRU -- so autograd delivers p.grad for every parameter, Embedding
+and GRU included.  The Categorical on the logits, the loss, the clipping and Adam stay in torch.
+
+The table is computed only for the mission ids that occur in the buffer (prepare(), once per train()
+call); the other rows stay zero and are never read for a sample.  The blob and the table are rebuilt
+for every evaluate_actions call: the weights change at every optimiser step.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+from .fused_policy import N_ACTIONS, _params, blob_words, mission_token_stacks
+
+
+def differentiable_blob(tensors):
+    """f32 [blob words]: torch.cat of the parameters in blob order, connected to them by autograd."""
+    return torch.cat([t.to(torch.float32).reshape(-1) for t in tensors])
+
+
+def mission_table_rows(policy, rows, stacks):
+    """f32 [256, n_stack, 128]: fused_policy.mission_table restricted to the flat rows `rows` (i64 [r], row =
+    mid * n_stack + v - 1; `stacks` i64 [r, 32 * n_stack] their token stacks), the rest zero -- with autograd."""
+    k, _ = _params(policy)
+    fe = policy.features_extractor
+    out = fe._mission_chunked(fe.extractors["mission"], stacks).to(torch.float32)
+    tab = torch.zeros((256 * k, 128), dtype=torch.float32, device=out.device)
+    return tab.index_copy(0, rows, out).reshape(256, k, 128)
+
+
+class _PolicyFn(torch.autograd.Function):
+    """(blob, mission_feat) -> (logits [B, 7], values [B]) of the samples `index` of `buf`."""
+
+    @staticmethod
+    def forward(ctx, blob, mission_feat, ev, buf, index):
+        blob, mission_feat = blob.detach().contiguous(), mission_feat.detach().contiguous()
+        ctx.ev, ctx.buf, ctx.index = ev, buf, index
+        ctx.save_for_backward(blob, mission_feat)
+        logits, values = ev.forward_raw(buf, index, blob, mission_feat)
+        return logits, values
+
+    @staticmethod
+    def backward(ctx, g_logits, g_values):
+        blob, mission_feat = ctx.saved_tensors
+        n = ctx.index.numel()
+        dev = blob.device
+        if g_logits is None:
+            g_logits = torch.zeros((n, N_ACTIONS), dtype=torch.float32, device=dev)
+        if g_values is None:
+            g_values = torch.zeros(n, dtype=torch.float32, device=dev)
+        gb, gm = ctx.ev.backward_raw(ctx.buf, ctx.index, blob, mission_feat, g_logits, g_values)
+        return gb, gm, None, None, None
+
+
+class FusedEvaluator:
+    """evaluate_actions of `policy` for samples of a CompactBuffer of `engine`, differentiable with respect to
+    every parameter.  max_groups: mgx_policy_grad.max_groups (0: the library's default)."""
+
+    def __init__(self, policy, engine, max_groups=0):
+        k, _ = _params(policy)                       # ValueError before anything touches the device
+        if engine is None or k != engine.n_stack:
+            raise ValueError("policy n_stack %d does not match the engine's" % k)
+        self.policy, self.engine, self.K = policy, engine, k
+        self.max_groups = int(max_groups)
+        self.words = int(engine.L.mgx_policy_blob_words(k))
+        if self.words != blob_words(k):
+            raise _lib.MgxError("blob layout mismatch: library %d words, packer %d" % (self.words, blob_words(k)))
+        self._stacks_all = mission_token_stacks(k, _lib.mission_tokens()).reshape(256 * k, 32 * k).to(engine.device)
+        self._rows = self._stacks = None
+        self._scratch = None
+        self._pol, self._out, self._grad = _lib.MgxPolicy(), _lib.MgxActOut(), _lib.MgxPolicyGrad()
+
+    def prepare(self, buf):
+        """Find the mission ids held by `buf` (one host sync): the table rows later calls compute."""
+        mids = torch.unique(buf.mids).to(torch.int64)
+        k = self.K
+        self._rows = (mids[:, None] * k + torch.arange(k, device=mids.device)[None, :]).reshape(-1)
+        self._stacks = self._stacks_all.index_select(0, self._rows)
+
+    def inputs(self):
+        """(blob, mission_feat): the kernel's two differentiable inputs from the policy's current parameters."""
+        _, tensors = _params(self.policy)
+        return differentiable_blob(tensors), mission_table_rows(self.policy, self._rows, self._stacks)
+
+    def _addr(self, buf, index):
+        e = self.engine
+        if buf.engine is not e:
+            raise ValueError("the buffer belongs to another engine")
+        P = ctypes.c_void_p
+        return (e.h, P(buf.rows.data_ptr()), P(buf.mids.data_ptr()), P(buf.starts.data_ptr()), buf.N,
+                buf.R if buf.ring else 0, P(index.data_ptr()), index.numel())
+
+    def forward_raw(self, buf, index, blob, mission_feat):
+        """mgx_policy_act mode 0 -> (logits f32 [B, 7], values f32 [B])."""
+        e, n = self.engine, index.numel()
+        logits = torch.empty((n, N_ACTIONS), dtype=torch.float32, device=e.device)
+        values = torch.empty(n, dtype=torch.float32, device=e.device)
+        p, o = self._pol, self._out
+        p.blob_dev, p.mission_feat_dev, p.mode = blob.data_ptr(), mission_feat.data_ptr(), 0
+        o.actions_dev = o.log_probs_dev = None
+        o.values_dev, o.logits_dev = values.data_ptr(), logits.data_ptr()
+        _lib.check(e.L.mgx_policy_act(*self._addr(buf, index), None, ctypes.byref(p), ctypes.byref(o), e._stream()),
+                   "mgx_policy_act")
+        return logits, values
+
+    def backward_raw(self, buf, index, blob, mission_feat, g_logits, g_values, scratch=None):
+        """mgx_policy_backward -> (grad_blob f32 [words], grad_mission_feat f32 [256, n_stack, 128])."""
+        e, n, k = self.engine, index.numel(), self.K
+        need = int(e.L.mgx_policy_grad_scratch_words(k, n, self.max_groups))
+        if scratch is None:
+            if self._scratch is None or self._scratch.numel() < need:
+                self._scratch = torch.empty(need, dtype=torch.float32, device=e.device)
+            scratch = self._scratch
+        gl = g_logits.to(torch.float32).contiguous()
+        gv = g_values.to(torch.float32).contiguous()
+        gb = torch.empty(self.words, dtype=torch.float32, device=e.device)
+        gm = torch.empty((256, k, 128), dtype=torch.float32, device=e.device)
+        g = self._grad
+        g.blob_dev, g.mission_feat_dev = blob.data_ptr(), mission_feat.data_ptr()
+        g.g_logits_dev, g.g_values_dev = gl.data_ptr(), gv.data_ptr()
+        g.grad_blob_dev, g.grad_mission_feat_dev = gb.data_ptr(), gm.data_ptr()
+        g.scratch_dev, g.scratch_words = scratch.data_ptr(), scratch.numel()
+        g.max_groups, g.reserved0 = self.max_groups, 0
+        _lib.check(e.L.mgx_policy_backward(*self._addr(buf, index), ctypes.byref(g), e._stream()),
+                   "mgx_policy_backward")
+        return gb, gm
+
+    def evaluate_actions(self, buf, index, actions):
+        """(values, log_prob, entropy) as ActorCriticPolicy.evaluate_actions on buf.gather(index)."""
+        if self._rows is None:
+            self.prepare(buf)
+        index = index.to(torch.int64).contiguous()
+        blob, table = self.inputs()
+        logits, values = _PolicyFn.apply(blob, table, self, buf, index)
+        dist = torch.distributions.Categorical(logits=logits)
+        return values, dist.log_prob(actions), dist.entropy()

@@ -66,6 +66,8 @@ class PPOConfig:
     layout: str = "compact"             # rollout storage: "compact" (mgx/compact.py) | "sb3" (stacked obs)
     fused_act: bool = False             # compact layout: act / bootstrap / last values through mgx_policy_act
                                         # (mgx/fused_policy.py; own sampling stream) instead of pol(gathered obs)
+    fused_train: bool = False           # compact layout: Trainer.train evaluates each minibatch through mgx_policy_act
+                                        # + mgx_policy_backward (mgx/fused_train.py) instead of pol.evaluate_actions
     env: dict = field(default_factory=lambda: dict(problem="multi", mission=2, size=8, num_objects=4))
 
 
@@ -218,6 +220,16 @@ class CompactRollout:
             yield (obs, self.actions[t, env], self.values[t, env], self.log_probs[t, env],
                    self.advantages[t, env], self.returns[t, env])
 
+    def minibatch_indices(self, batch_size, perm):
+        """minibatches() without the gather: the observations named by their flat compact-buffer indices
+        (CompactBuffer.index), for FusedEvaluator.evaluate_actions."""
+        T = self.T
+        for s in range(0, perm.numel(), batch_size):
+            idx = perm[s:s + batch_size]
+            env, t = idx // T, idx % T
+            yield (self.buf.index(t, env), self.actions[t, env], self.values[t, env], self.log_probs[t, env],
+                   self.advantages[t, env], self.returns[t, env])
+
 
 class CompactRolloutCollector:
     """OnPolicyAlgorithm.collect_rollouts over an MgxEngine with the compact layout: per step one
@@ -305,6 +317,9 @@ class Trainer:
         self.gen = torch.Generator(device=next(policy.parameters()).device)
         self.gen.manual_seed(cfg.seed)
         self.world = torch.distributed.get_world_size(group) if group is not None else 1
+        self.fused = None              # FusedEvaluator of the rollout's engine (cfg.fused_train), made on first use
+        if getattr(cfg, "fused_train", False) and cfg.layout != "compact":
+            raise ValueError("fused_train needs layout='compact'")
 
     def global_adv_stats(self, buf):
         s = buf.adv_stats.clone()
@@ -340,10 +355,21 @@ class Trainer:
             g_mean, g_std, _ = self.global_adv_stats(buf)
         n = buf.T * buf.N
         stats = dict(pg=[], vf=[], ent=[], kl=[], clipfrac=[])
+        fused = None
+        if getattr(cfg, "fused_train", False):
+            if self.fused is None or self.fused.engine is not buf.buf.engine:
+                from .fused_train import FusedEvaluator
+                self.fused = FusedEvaluator(pol, buf.buf.engine)
+            fused = self.fused
+            fused.prepare(buf.buf)         # the mission ids of this rollout: the table rows each minibatch computes
         for epoch in range(cfg.n_epochs):
             perm = perm_fn(n) if perm_fn else torch.randperm(n, generator=self.gen, device=self.gen.device)
-            for obs, actions, old_v, old_lp, adv, ret in buf.minibatches(cfg.batch_size, perm):
-                values, log_prob, entropy = pol.evaluate_actions(obs, actions)
+            batches = buf.minibatches if fused is None else buf.minibatch_indices
+            for obs, actions, old_v, old_lp, adv, ret in batches(cfg.batch_size, perm):
+                if fused is None:
+                    values, log_prob, entropy = pol.evaluate_actions(obs, actions)
+                else:                      # obs: flat compact-buffer indices
+                    values, log_prob, entropy = fused.evaluate_actions(buf.buf, obs, actions)
                 if cfg.normalize_advantage and adv.numel() > 1:
                     if g_mean is not None:
                         adv = (adv - g_mean.float()) / (g_std.float() + 1e-8)
