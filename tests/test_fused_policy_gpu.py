@@ -13,7 +13,11 @@ n_stack 5..8 (mgx_policy_kernel<5..8>: X = 37 K rows of LDS, 16 direction bits, 
 columns up to 4 K - 1, mission_feat[mid][v-1] with v up to 8): the ring is 3 or 4 blocks of 3 rows and the walk-back
 crosses up to three of them.  The reference observation there is still buf.gather_step, which tests/test_compact.py
 pins to the FrameStackOracle at those depths; at n_stack 8 the run itself also compares the final gathered observation
-with the C oracle's frames stacked by the FrameStackOracle (_oracle_stacks)."""
+with the C oracle's frames stacked by the FrameStackOracle (_oracle_stacks).
+
+Every gtg episode has mission id 3: each lane of a tile reads the same mission-feature row.  The *_many_missions tests
+run the same setup on MULTI (multi 8x8, mission=None: dozens of mission ids below 128 per tile), the *_high_mission_ids
+tests on FULL (ids 128..132 next to ids below 128); both pin the n_stack 8 observation to the oracle as well."""
 import copy
 import ctypes
 
@@ -28,6 +32,8 @@ pytestmark = pytest.mark.gpu
 
 N_ENVS, T_RING, STEPS = 70, 3, 40
 ENV = dict(problem="gtg", mission=5, size=6, num_objects=2)
+MULTI = dict(problem="multi", mission=None, size=8, num_objects=4)
+FULL = dict(problem="full", mission=None, size=8, num_objects=4)
 M64 = (1 << 64) - 1
 
 
@@ -62,11 +68,11 @@ def _cat(obs_list):
     return {k: torch.cat([o[k] for o in obs_list]) for k in obs_list[0]}
 
 
-def _oracle_stacks(k, actions):
+def _oracle_stacks(k, actions, env=ENV):
     """The stacked observation before every step and after the last one: the C oracle stepped with `actions`
     ([steps, N_ENVS]), its frames stacked by the numpy VecTransposeImage + VecFrameStack restatement."""
     import oracle as O
-    ov = O.OracleVec(ENV["problem"], ENV["mission"], ENV["size"], ENV["num_objects"], N_ENVS, 42)
+    ov = O.OracleVec(env["problem"], env["mission"], env["size"], env["num_objects"], N_ENVS, 42)
     fs = O.FrameStackOracle(N_ENVS, k)
 
     def raw(img, dr, mi):
@@ -91,28 +97,30 @@ class Run:
 _RUNS = {}
 
 
-def _run(k):
-    """One 40-step trajectory per n_stack, everything the tests compare recorded once."""
+def _run(k, env=ENV):
+    """One 40-step trajectory per (n_stack, env), everything the tests compare recorded once."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    if k in _RUNS:
-        return _RUNS[k]
+    key = (k, tuple(sorted(env.items())))
+    if key in _RUNS:
+        return _RUNS[key]
     from mgx import MgxEngine
     from mgx.compact import CompactBuffer
     from mgx.fused_policy import FusedActor
     r = Run()
     r.pol = _policy(k).cuda()
     r.pol64 = copy.deepcopy(r.pol).cpu().double()
-    r.eng = MgxEngine(n_envs=N_ENVS, n_stack=k, terminal_mode="truncated", mission_dtype=torch.uint8, **ENV)
+    r.eng = MgxEngine(n_envs=N_ENVS, n_stack=k, terminal_mode="truncated", mission_dtype=torch.uint8, **env)
     r.buf = CompactBuffer(r.eng, T_RING, ring=True)
     r.actor = FusedActor(r.pol, r.eng, seed=1234)
     r.eng.reset()
     r.buf.observe(0)
     g = torch.Generator().manual_seed(5)
-    obs, lg, val, act, lp, starts, stepped = [], [], [], [], [], 0, []
+    obs, lg, val, act, lp, starts, stepped, mids = [], [], [], [], [], 0, [], []
     t = 0
     for step in range(STEPS + 1):
         obs.append({kk: v.clone() for kk, v in r.buf.gather_step(t, f32=False).items()})
+        mids.append(r.buf.mids[r.buf.row(t)].cpu().long())
         l, v = r.actor.logits(r.buf, t)
         a, v1, p = r.actor.act(r.buf, t, deterministic=True)
         assert torch.equal(v, v1)                          # modes 0 and 1: the same forward pass
@@ -131,10 +139,12 @@ def _run(k):
     if k == 8:
         # the reference observation of this file is the gather's: pin it to the oracle here too (the final step, whose
         # stack was built across carried-over ring blocks)
-        want = _oracle_stacks(k, torch.stack(stepped).numpy())[-1]
+        want = _oracle_stacks(k, torch.stack(stepped).numpy(), env)[-1]
         for kk in ("image", "direction", "mission"):
             assert np.array_equal(obs[-1][kk].cpu().numpy().astype(np.int64), want[kk].astype(np.int64)), kk
     r.obs = _cat(obs)
+    r.mid = torch.cat(mids)                                # mission id of every sample, launch by launch
+    r.v = (r.obs["direction"].reshape(-1, k, 4).sum(2) > 0).sum(1).cpu()
     r.logits, r.values, r.actions, r.log_probs = torch.cat(lg), torch.cat(val), torch.cat(act), torch.cat(lp)
     r.ref_logits, r.ref_values = _ref64(r.pol64, r.obs)
     r.ref_logp = torch.log_softmax(r.ref_logits, 1)
@@ -145,14 +155,11 @@ def _run(k):
                      log_probs=float((t_logp - r.ref_logp).abs().max()))
     r.tol = {kk: 4.0 * v for kk, v in r.e_torch.items()}
     r.eng.poll_error()
-    _RUNS[k] = r
+    _RUNS[key] = r
     return r
 
 
-@pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 6, 7, 8])
-def test_forward_parity(k):
-    """logits, values and mode-1 log-probs of every sample of every step within 4 x e_torch of the fp64 module."""
-    r = _run(k)
+def _forward_parity(r, k, tag=""):
     assert r.logits.shape == (N_ENVS * (STEPS + 1), 7)
     assert r.episode_ends > N_ENVS                         # starts inside the stack windows were exercised
     n_empty = int((r.obs["direction"].reshape(-1, k, 4).sum(2) == 0).any(1).sum())
@@ -163,11 +170,51 @@ def test_forward_parity(k):
     lp_ref = r.ref_logp.gather(1, r.actions[:, None])[:, 0]
     dev["log_probs"] = float((r.log_probs - lp_ref).abs().max())
     for q in ("logits", "values", "log_probs"):
-        print("n_stack %d %s: kernel max |dev| %.3e, torch fp32 (GPU) max |dev| %.3e, bound %.3e"
-              % (k, q, dev[q], r.e_torch[q], r.tol[q]))
+        print("%sn_stack %d %s: kernel max |dev| %.3e, torch fp32 (GPU) max |dev| %.3e, bound %.3e"
+              % (tag, k, q, dev[q], r.e_torch[q], r.tol[q]))
     for q in ("logits", "values", "log_probs"):
         assert r.e_torch[q] > 0
         assert dev[q] <= r.tol[q], (q, dev[q], r.e_torch[q])
+
+
+@pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 6, 7, 8])
+def test_forward_parity(k):
+    """logits, values and mode-1 log-probs of every sample of every step within 4 x e_torch of the fp64 module."""
+    _forward_parity(_run(k), k)
+
+
+def _launch_tiles(r):
+    """[(mid, v)] of the full 64-sample tile of every launch (70 envs: one full tile and a 6-lane tail)."""
+    pairs = list(zip(r.mid.tolist(), r.v.tolist()))
+    return [pairs[i:i + 64] for i in range(0, len(pairs), N_ENVS)]
+
+
+def _assert_many_keys(r, k):
+    """Some launch's full tile holds >= 9 distinct (mission id, v) keys, and >= 12 mission ids occur."""
+    counts = [len(set(t)) for t in _launch_tiles(r)]
+    print("multi n_stack %d: distinct (mid, v) keys per launch tile: min %d, max %d; %d mission ids in all"
+          % (k, min(counts), max(counts), len(set(r.mid.tolist()))))
+    assert max(counts) >= 9 and len(set(r.mid.tolist())) >= 12
+
+
+@pytest.mark.parametrize("k", [4, 8])
+def test_forward_parity_many_missions(k):
+    """test_forward_parity on MULTI: every lane of a tile fetches its own mission-feature row."""
+    r = _run(k, MULTI)
+    _assert_many_keys(r, k)
+    _forward_parity(r, k, "multi ")
+
+
+@pytest.mark.parametrize("k", [4, 8])
+def test_forward_parity_high_mission_ids(k):
+    """test_forward_parity on FULL: one tile holds mission ids >= 128 (drop, move) next to ids below 128."""
+    r = _run(k, FULL)
+    tiles = _launch_tiles(r)
+    high = [sum(m >= 128 for m, _ in t) for t in tiles]
+    print("full n_stack %d: samples with mission id >= 128 per launch tile: min %d, max %d; ids %s"
+          % (k, min(high), max(high), sorted(set(r.mid.tolist()))))
+    assert any(0 < h < 64 for h in high) and int(r.mid.max()) <= 132
+    _forward_parity(r, k, "full ")
 
 
 @pytest.mark.parametrize("k", [1, 3, 4, 5, 8])
@@ -247,11 +294,7 @@ def test_splitmix_restatement_matches_random_actions():
     assert out.cpu().tolist() == want
 
 
-@pytest.mark.parametrize("k", [1, 3, 4, 5, 8])
-def test_sampling(k):
-    """Mode 2: the action is the inverse-cdf choice of the documented u over the kernel's own logits; log-prob =
-    log_softmax(logits)[action]; (seed, counter) reproduces; the launch advances the counter."""
-    r = _run(k)
+def _sampling(r):
     actor, buf, t = r.actor, r.buf, r.t
     actor.counter.zero_()
     a0, v0, lp0, lg0 = actor.act(buf, t, logits=True)
@@ -281,6 +324,21 @@ def test_sampling(k):
     assert float((lp0.double().cpu() - lsm).abs().max()) <= r.tol["log_probs"]
     assert torch.equal(lg0.double().cpu(), r.logits[-N_ENVS:]) and torch.equal(v0.double().cpu(), r.values[-N_ENVS:])
     assert len(set(a0.cpu().tolist())) > 1
+
+
+@pytest.mark.parametrize("k", [1, 3, 4, 5, 8])
+def test_sampling(k):
+    """Mode 2: the action is the inverse-cdf choice of the documented u over the kernel's own logits; log-prob =
+    log_softmax(logits)[action]; (seed, counter) reproduces; the launch advances the counter."""
+    _sampling(_run(k))
+
+
+@pytest.mark.parametrize("k", [4, 8])
+def test_sampling_many_missions(k):
+    """test_sampling on MULTI."""
+    r = _run(k, MULTI)
+    _assert_many_keys(r, k)
+    _sampling(r)
 
 
 def test_ring_shorter_than_stack_rejected():

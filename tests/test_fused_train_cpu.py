@@ -131,6 +131,84 @@ def test_differentiable_table():
         assert float(b.abs().max()) > 0 and dev <= bound, name
 
 
+class _HostEngine:
+    """What FusedEvaluator.prepare / inputs and CompactRollout read of an engine, on the CPU."""
+
+    def __init__(self, lib, n_envs, n_stack):
+        self.L, self.n, self.n_stack, self.device = lib, n_envs, n_stack, torch.device("cpu")
+
+
+def test_table_rows_of_mixed_mission_ids(lib):
+    """n_stack 4, a buffer whose mission ids are 3, 37, 128, 132 and 255 (below and above 128, the last one unused:
+    32 zero tokens): FusedEvaluator.prepare + inputs give fused_policy.mission_table on the rows mid * 4 + v - 1 of
+    those ids at every v (within 4 eps32: the GRU runs on another batch) and exact zeros on the other 1,004 rows; the
+    gradient of a cotangent that is non-zero on every row reaches only those 20 rows: the Embedding weight's
+    gradient is non-zero on exactly the tokens those missions hold (0, the padding, among them)."""
+    k = 4
+    ids = [3, 37, 128, 132, 255]
+    torch.manual_seed(13)
+    pol = ActorCriticPolicy(n_stack=k)
+    pol.train(False)
+    ev = ft.FusedEvaluator(pol, _HostEngine(lib, 7, k))
+
+    class Buf:
+        mids = torch.tensor(ids * 3 + [37, 3], dtype=torch.uint8).reshape(1, 17)
+
+    ev.prepare(Buf)
+    blob, tab = ev.inputs()
+    assert tab.shape == (256, k, 128) and tab.requires_grad and blob.numel() == fp.blob_words(k)
+    full = fp.mission_table(pol)
+    mask = torch.zeros((256, k), dtype=torch.bool)
+    mask[ids] = True
+    assert float(full[mask].abs().max()) > 0.1
+    assert torch.allclose(tab.detach()[mask], full[mask], rtol=0, atol=4 * torch.finfo(torch.float32).eps)
+    assert not tab.detach()[~mask].any()
+    # rows of two ids differ by far more than that tolerance (the v rows of one id do not: after the mission's 32
+    # tokens the GRU has all but forgotten the zero frames before them; the exact zeros pin those)
+    rows = full[ids, k - 1]
+    assert float(torch.cdist(rows, rows).fill_diagonal_(1.0).min()) > 1e-5
+    R = torch.randn((256, k, 128), generator=torch.Generator().manual_seed(9))
+    emb = pol.features_extractor.extractors["mission"][0].weight
+    g = torch.autograd.grad((tab * R).sum(), emb)[0]
+    tokens = torch.as_tensor(_lib.mission_tokens()).long()
+    held = torch.zeros(32, dtype=torch.bool)
+    held[tokens[ids].reshape(-1)] = True
+    held[0] = True
+    assert 3 < int(held.sum()) < 32
+    assert g.shape == (32, 32) and not g[~held].any()
+    assert all(bool(g[t].any()) for t in held.nonzero().flatten().tolist())
+
+
+def test_minibatch_indices_pair_each_sample_with_its_own_row(lib):
+    """CompactRollout.minibatch_indices, T = 4 and N = 5 in the third ring block: flat index i of the permutation is
+    (env, t) = (i // T, i % T) (SB3's env-major flatten); the yielded compact index is ((block * T + t - 1) mod R) *
+    N + env and the five tensors beside it are that (t, env)'s."""
+    from mgx.ppo import CompactRollout
+    T, N, k = 4, 5, 4
+    ro = CompactRollout(_HostEngine(lib, N, k), T)
+    ro.buf.carry_over()
+    ro.buf.carry_over()
+    assert (ro.buf.blocks, ro.buf.R, ro.buf.block) == (2, 8, 0)
+    ro.buf.carry_over()                                       # block 1: observation 0 is the last row of block 0
+    tag = (100 * torch.arange(T)[:, None] + torch.arange(N)[None, :])
+    ro.actions.copy_(tag)
+    for j, a in enumerate((ro.values, ro.log_probs, ro.advantages, ro.returns)):
+        a.copy_(tag.float() + 0.125 * (j + 1))
+    perm = torch.randperm(T * N, generator=torch.Generator().manual_seed(2))
+    seen = 0
+    for s, out in enumerate(ro.minibatch_indices(8, perm)):
+        index, actions = out[0], out[1]
+        for j in range(index.numel()):
+            i = int(perm[8 * s + j])
+            env, t = i // T, i % T
+            assert int(index[j]) == ((1 * T + t - 1) % 8) * N + env
+            assert int(actions[j]) == 100 * t + env
+            for q in range(4):
+                assert float(out[2 + q][j]) == 100 * t + env + 0.125 * (q + 1)
+            seen += 1
+    assert seen == T * N
+
+
 def test_fused_evaluator_rejects_other_architectures():
     """The same ValueError as FusedActor, before the engine is touched."""
     for pol in (ActorCriticPolicy(n_stack=2, net_arch={"pi": [32, 32], "vf": [64, 64]}),
