@@ -16,7 +16,11 @@ env owns an MT19937 seeded 42.  We reproduce this by giving env i its own
 first reset with seed 42+i (make_vec_env(seed=42) / VecEnv.seed), later resets
 are unseeded (PCG64 stream continues).
 
-Usage:  python tests/golden/make_golden.py  [--quick]
+Usage:  python tests/golden/make_golden.py  [--only NAME] [--agent random|scripted]
+
+--agent random (the default) draws every action uniformly from 0..6.  --agent scripted drives the envs
+with tests/golden/scripted_agent.py (deep episodes: unlocks, truncations, endings on the last step) and
+writes the DEEP configs as deep_<name>.npz, which also record `agent_name` and `agent_seed`.
 """
 import argparse
 import os
@@ -30,7 +34,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "oracle", "refshim"))
 
+sys.path.insert(0, HERE)
+
 from loader import load_reference, make_cfg  # noqa: E402
+import scripted_agent as SA  # noqa: E402
 
 # Live-lock policy (engine-defined; the reference would hang):
 # a reset *attempt* may consume at most LIVELOCK_WORDS MT words.  The attempt
@@ -170,10 +177,22 @@ def target_info(env):
     return tx, ty, ta
 
 
-def run_config(name, cfg, n, T, seed_actions=1234, manual=False):
+def agent_view(env, S):
+    """One reference env's state as the scripted agent sees it (the dump layout)."""
+    ax, ay, adir, carry, sc, md, _ = env_state(env)
+    return SA.View(S, encode_grid(env.unwrapped.grid).tolist(), [ax, ay, adir], list(carry),
+                   list(target_info(env)), md, sc)
+
+
+def run_config(name, cfg, n, T, seed_actions=1234, manual=False, agent="random"):
     S = cfg.env.size
     vec = RefVec(cfg, n, manual=manual)
-    acts = np.random.default_rng(seed_actions).integers(0, 7, (T, n)).astype(np.int8)
+    if agent == "scripted":
+        assert T % 16 == 0
+        acts = np.zeros((T, n), np.int8)
+        ctx = [SA.AgentCtx(seed_actions, i) for i in range(n)]
+    else:
+        acts = np.random.default_rng(seed_actions).integers(0, 7, (T, n)).astype(np.int8)
     d = {}
 
     def alloc(key, shape, dtype, fill=0):
@@ -230,6 +249,8 @@ def run_config(name, cfg, n, T, seed_actions=1234, manual=False):
     missions = {}
     for t in range(T):
         for i in range(n):
+            if agent == "scripted":
+                acts[t, i] = SA.act(agent_view(vec.envs[i], S), ctx[i])
             obs, r, term, trunc, _ = vec.step_env(i, acts[t, i])
             u = vec.envs[i].unwrapped
             missions[u.mission] = obs["mission"].astype(np.uint8)
@@ -252,6 +273,9 @@ def run_config(name, cfg, n, T, seed_actions=1234, manual=False):
                 rec_reset("r_", (t, i), i, obs2)
                 descs.append((t, i, vec.envs[i].unwrapped.llm_description))
     d["actions"] = acts
+    if agent == "scripted":
+        d["agent_name"] = np.array("scripted")     # (`agent` is the per-step agent state)
+        d["agent_seed"] = np.array(seed_actions, np.int64)
     d["desc_t"] = np.array([x[0] for x in descs], np.int32)
     d["desc_env"] = np.array([x[1] for x in descs], np.int32)
     d["desc_text"] = np.array([x[2] for x in descs])
@@ -305,22 +329,34 @@ CONFIGS += [
 ]
 
 
+# the configs --agent scripted runs (written as deep_<name>.npz)
+DEEP = ("multi_all_s8", "obst_multi_all_s8", "novis_multi_all_s8", "ado_multi_all_s8", "manual_multi_all_s8",
+        "multi_pkp_s11", "multi_all_s11_o8", "multi_tgl_s16", "multi_gtg_s16", "novis_obst_multi_tgl_s16",
+        "single_full_s8", "single_mov_s8", "single_drp_s8", "single_opn_s8")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=16)
     ap.add_argument("--T", type=int, default=512)
     ap.add_argument("--only", default=None)
+    ap.add_argument("--agent", choices=("random", "scripted"), default="random")
     args = ap.parse_args()
+    scripted = args.agent == "scripted"
     out_dir = os.path.join(HERE, "traj")
     os.makedirs(out_dir, exist_ok=True)
     for name, kw in CONFIGS:
         if args.only and args.only not in name:
             continue
+        if scripted and name not in DEEP:
+            continue
         t0 = time.time()
         kw = dict(kw)
         manual = kw.pop("manual", False)
         cfg = make_cfg(**kw)
-        d = run_config(name, cfg, args.n, args.T, manual=manual)
+        d = run_config(name, cfg, args.n, args.T, manual=manual, agent=args.agent)
+        if scripted:
+            name = "deep_" + name
         np.savez_compressed(os.path.join(out_dir, name + ".npz"), **d)
         print("%-22s %6.1fs resets=%d livelocks=%d" % (
             name, time.time() - t0, int((d["terminated"] | d["truncated"]).sum()),

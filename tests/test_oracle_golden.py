@@ -12,7 +12,7 @@ FIXTURES = TC.fixtures()
 
 
 def test_fixtures_present():
-    assert len(FIXTURES) == 39
+    assert len(FIXTURES) == 53                    # 39 random-action runs + 14 scripted-agent (deep_*) runs
 
 
 def test_manual_fixtures_hold_premature_dones():
@@ -35,13 +35,41 @@ def test_oracle_matches_reference_fixture(path):
 
 
 def test_fixture_covers_quirks():
-    """The fixtures exercise the paths that matter: live-locks (S=8), truncation,
-    mission completion with stored reward, goal termination."""
+    """The fixtures exercise the paths that matter.  Over the whole set: live-locks (S=8), truncation,
+    mission completion with stored reward, goal termination.  Per scripted-agent fixture (deep_*,
+    tests/golden/scripted_agent.py) floors on the deep-episode events of TC.events -- conditions on the
+    inputs, not measurements of the code under test: the time limit reached at every size, locked doors
+    opened with the carried key, carried objects consumed by a same-colour door (Q4), paid rewards,
+    truncations with a completed mission still stored (Q2), steps that terminate and truncate at once,
+    a locked door toggled with the wrong key."""
     tot_ll = tot_trunc = tot_goal = tot_stored = 0
+    trunc_md = trunc_md_s16 = wrong_key = n_deep = 0
     for p in FIXTURES:
         d = dict(np.load(p))
+        name = p.split("/")[-1][:-4]
         tot_ll += int(d["livelock"].sum() + d["reset0_livelock"].sum())
         tot_trunc += int(d["truncated"].sum())
         tot_goal += int(((d["reward"] > 0) & (d["terminated"] == 1)).sum())
         tot_stored += int(np.isfinite(d["stored_reward"]).sum())
-    assert tot_ll > 0 and tot_goal > 0 and tot_stored > 0
+        if not name.startswith("deep_"):
+            continue
+        n_deep += 1
+        assert str(d["agent_name"]) == "scripted" and int(d["meta"][2]) % 16 == 0, name
+        e = TC.events(d)
+        S = e["size"]
+        multi, ado = "multi" in name, "ado_" in name
+        assert e["max_step_count"] == S * S and e["truncations"] >= 10, (name, e)
+        if multi and not ado:
+            assert e["unlocks"] >= 20 and e["q4"] >= 20, (name, e)
+        if "_mov_" not in name:
+            assert e["paid"] >= 90, (name, e)
+        if "_gtg_" not in name:                      # (every other mission pays on its `done`)
+            assert e["done_paid"] >= 30, (name, e)
+        assert e["term_and_trunc"] >= (3 if S == 8 else 1), (name, e)
+        trunc_md += e["trunc_mission_done"]
+        trunc_md_s16 += e["trunc_mission_done"] if S == 16 else 0
+        wrong_key += e["wrong_key"]
+    assert tot_ll > 0 and tot_goal > 0 and tot_stored > 0 and tot_trunc > 0
+    assert n_deep == 14
+    assert trunc_md >= 50 and trunc_md_s16 >= 1, (trunc_md, trunc_md_s16)
+    assert wrong_key >= 1

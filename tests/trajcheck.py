@@ -84,6 +84,50 @@ def compare(src, d, T=None, check_state=True):
     return None
 
 
+_DV = np.array([(1, 0), (0, 1), (-1, 0), (0, -1)])
+
+
+def events(d):
+    """Counts of the step-logic events a fixture holds, from its recorded arrays alone (`grid`, `agent`,
+    `carrying`, `mission_done` are the states after each step and before the reset; the state a step
+    started from is the previous step's, or the new episode's where that step ended one)."""
+    a = d["actions"].astype(np.int64)
+    T, n = a.shape
+    term, trunc = d["terminated"].astype(bool), d["truncated"].astype(bool)
+    done = term | trunc
+    prev_done = np.concatenate([np.zeros((1, n), bool), done[:-1]])
+
+    def before(key, first, after_reset):
+        shifted = np.concatenate([first[None], d[key][:-1]])
+        reset = np.concatenate([first[None], after_reset[:-1]])
+        return np.where(prev_done.reshape((T, n) + (1,) * (shifted.ndim - 2)), reset, shifted)
+
+    grid0 = before("grid", d["reset0_grid"], d["r_grid"])
+    agent0 = before("agent", d["reset0_agent"], d["r_agent"]).astype(np.int64)
+    carry0 = before("carrying", np.zeros((n, 4), np.uint8), np.zeros((T, n, 4), np.uint8))
+    fx = agent0[..., 0] + _DV[agent0[..., 2], 0]
+    fy = agent0[..., 1] + _DV[agent0[..., 2], 1]
+    tt, ii = np.meshgrid(np.arange(T), np.arange(n), indexing="ij")
+    front0, front1 = grid0[tt, ii, fx, fy], d["grid"][tt, ii, fx, fy]
+    toggle = a == 5
+    at_locked = toggle & (front0[..., 0] == 4) & (front0[..., 2] == 2)
+    has_key = carry0[..., 0] == 5
+    S = int(d["meta"][0])
+    sc = d["step_count"]
+    return dict(
+        size=S,
+        unlocks=int((at_locked & has_key & (front1[..., 2] == 0)).sum()),
+        q4=int((toggle & ~done & (carry0[..., 0] != 0) & (d["carrying"][..., 0] == 0)).sum()),
+        wrong_key=int((at_locked & has_key & (carry0[..., 1] != front0[..., 1]) & (front1[..., 2] == 2)).sum()),
+        truncations=int(trunc.sum()),
+        max_step_count=int(sc.max()),
+        paid=int((d["reward"] > 0).sum()),
+        done_paid=int(((a == 6) & (d["reward"] > 0)).sum()),
+        trunc_mission_done=int((trunc & (d["mission_done"] == 1)).sum()),
+        term_and_trunc=int((term & trunc).sum()),
+    )
+
+
 def _diff_envs(a, b):
     a = np.asarray(a)
     b = np.asarray(b)
