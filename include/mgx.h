@@ -258,9 +258,10 @@ mgx_status mgx_gather_ring(const mgx_handle *h, const uint8_t *rows_dev, const u
  *    7. value_net_body L0, L1   as 5 and 6
  *    8. action_net              W[7][64], b[7]
  *    9. value_net               W[1][64], b[1]
- * (46,984 words at K = 4).  The mission GRU does not run on the device: the valid slots of a stack are
+ * (46,984 words at K = 4).  The mission GRU does not run in this kernel: the valid slots of a stack are
  * contiguous from the newest and share one mission id, so the mission features take only (mission id,
- * v = number of valid slots) values, and the caller tabulates them with the policy's own Embedding + GRU:
+ * v = number of valid slots) values, and the caller tabulates them with the policy's own Embedding + GRU
+ * (in torch, or with mgx_mission_forward below):
  * mission_feat[mid][v-1][:] = features of K - v zero frames followed by v copies of mid's 32 tokens. */
 int64_t mgx_policy_blob_words(int n_stack);   /* host only; -1 unless 1 <= n_stack <= 8 */
 
@@ -300,8 +301,8 @@ mgx_status mgx_policy_act(const mgx_handle *h, const uint8_t *rows_dev, const ui
  *    grad_blob         = sum over samples of d(g_logits . logits + g_values * value) / d blob
  *    grad_mission_feat = the same derivative with respect to the mission-feature table
  * (the forward half of a training step is mgx_policy_act in mode 0 with logits_dev set).  The Embedding
- * and the GRU never run on the device: the caller back-propagates grad_mission_feat through its own
- * differentiable table.  fp32 with fp32 accumulation; MaxPool's gradient goes to the first maximum in
+ * and the GRU do not run in this call: the caller back-propagates grad_mission_feat through its own
+ * differentiable table (in torch, or with mgx_mission_backward below).  fp32 with fp32 accumulation; MaxPool's gradient goes to the first maximum in
  * window order, ReLU's where the pre-activation is positive.
  *
  * Summation order.  At most `groups` workgroups run (max_groups, or 256 -- one per CU of an MI355X -- when
@@ -337,6 +338,56 @@ mgx_status mgx_policy_backward(const mgx_handle *h, const uint8_t *rows_dev, con
                                const uint8_t *starts_dev, int64_t n_envs, int64_t ring_rows,
                                const int64_t *index_dev, int64_t n_samples, const mgx_policy_grad *g,
                                void *stream);
+
+/* ---- Mission encoder: Embedding + GRU forward and backward (added within ABI 9) --------------------
+ * The reference's mission extractor for n_rows independent token sequences of length seq_len:
+ * Embedding(32, 32) -> GRU(32, 128, one layer, bias, batch_first), h0 = 0, output = the last hidden state.
+ * Gate order and bias placement are torch's: r = sigmoid(W_ir x + b_ir + W_hr h + b_hr), z likewise,
+ * n = tanh(W_in x + b_in + r * (W_hn h + b_hn)), h' = (1 - z) * n + z * h.  fp32 with fp32 accumulation.
+ * Token values are masked with & 31.  These calls take no engine handle: they read nothing of an engine.
+ *
+ * One persistent kernel per direction keeps W_hh in registers over all seq_len steps.  With a workspace
+ * the forward records, per (row, t), what the backward needs; the backward walks the steps in reverse,
+ * replaces the records by the gate cotangents and then forms the weight gradients from them off the
+ * serial chain (an fp32 MFMA product over (row, t) in chunks whose number and length depend on (n_rows,
+ * seq_len) only, added in chunk order).  No float atomics: every output is bitwise reproducible for a
+ * given (n_rows, seq_len).  Embedding-gradient rows of tokens that never occur are exactly zero.
+ * The workspace is caller-owned and need not be zeroed. */
+int64_t mgx_mission_workspace_words(int64_t n_rows, int seq_len);
+                                    /* host only; -1 unless 1 <= n_rows <= 2048, 1 <= seq_len <= 256 */
+
+typedef struct mgx_mission_params { /* fp32, torch's row-major layouts; w_ih_dev and w_hh_dev 16-byte aligned */
+    const float *embedding_dev;     /* [32][32]   Embedding.weight */
+    const float *w_ih_dev;          /* [384][32]  GRU.weight_ih_l0 (r | z | n) */
+    const float *w_hh_dev;          /* [384][128] GRU.weight_hh_l0 */
+    const float *b_ih_dev;          /* [384]      GRU.bias_ih_l0 */
+    const float *b_hh_dev;          /* [384]      GRU.bias_hh_l0 */
+} mgx_mission_params;
+
+typedef struct mgx_mission_grads {  /* the same shapes; every one OVERWRITTEN */
+    float *embedding_dev;
+    float *w_ih_dev;
+    float *w_hh_dev;
+    float *b_ih_dev;
+    float *b_hh_dev;
+} mgx_mission_grads;
+
+/* features_dev f32 [n_rows][128].  workspace_dev NULL: inference only; else f32 [workspace_words] with
+ * workspace_words >= mgx_mission_workspace_words(n_rows, seq_len).  The features are bitwise the same
+ * with and without a workspace.  Only enqueues on `stream` (no allocation, no host sync; capturable).
+ * MGX_ERR_INVALID before any HIP call for: a null pointer (workspace_dev excepted), sizes out of range,
+ * a workspace that is too short. */
+mgx_status mgx_mission_forward(const uint8_t *tokens_dev /* u8 [n_rows][seq_len] */, int64_t n_rows, int seq_len,
+                               const mgx_mission_params *p, float *features_dev, float *workspace_dev,
+                               int64_t workspace_words, void *stream);
+
+/* g_features_dev f32 [n_rows][128]: the cotangent of the forward's features.  workspace_dev: as the forward
+ * of the same tokens and parameters left it; clobbered.  Writes the five gradients of g.  Only enqueues
+ * on `stream` (four launches; no allocation, no host sync; capturable).  MGX_ERR_INVALID before any HIP
+ * call for: any null pointer, sizes out of range, a workspace that is too short. */
+mgx_status mgx_mission_backward(const uint8_t *tokens_dev, int64_t n_rows, int seq_len, const mgx_mission_params *p,
+                                const float *g_features_dev, float *workspace_dev, int64_t workspace_words,
+                                const mgx_mission_grads *g, void *stream);
 
 /* Makes `stream` wait for the in-flight refill, if any (no host sync). */
 mgx_status mgx_join(mgx_handle *h, void *stream);

@@ -2729,6 +2729,7 @@ __global__ __launch_bounds__(256) void mgx_gather_kernel(const uint8_t *__restri
 
 #include "mgx_policy.h"   // mgx_policy_act's kernel (fused actor-critic forward over compact rows)
 #include "mgx_policy_grad.h"   // mgx_policy_backward's kernels (its gradient)
+#include "mgx_mission.h"   // mgx_mission_forward / mgx_mission_backward: the mission Embedding + GRU
 
 // ================================================================== host side
 thread_local std::string g_last_error;
@@ -3897,6 +3898,77 @@ mgx_status mgx_policy_backward(const mgx_handle *h, const uint8_t *rows_dev, con
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(mgx_policy_fold_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const float *)g->scratch_dev, a.groups, words, g->grad_blob_dev);
+    HIP_TRY(hipGetLastError());
+    return MGX_OK;
+}
+
+// ---- mission Embedding + GRU (mgx_mission.h): no engine handle, nothing of an engine is read
+static int mission_chunks(int64_t pairs) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(MS_MAX_CHUNKS, (pairs + MS_KCHUNK - 1) / MS_KCHUNK));
+}
+
+int64_t mgx_mission_workspace_words(int64_t n_rows, int seq_len) {
+    if (n_rows < 1 || n_rows > MS_MAX_ROWS || seq_len < 1 || seq_len > MS_MAX_SEQ) return -1;
+    const int64_t pairs = n_rows * seq_len;
+    return pairs * MS_REC + (int64_t)mission_chunks(pairs) * MS_SLAB + MS_V * MS_G;
+}
+
+static bool mission_params_ok(const mgx_mission_params *p) {
+    return p && p->embedding_dev && p->w_ih_dev && p->w_hh_dev && p->b_ih_dev && p->b_hh_dev;
+}
+
+mgx_status mgx_mission_forward(const uint8_t *tokens_dev, int64_t n_rows, int seq_len, const mgx_mission_params *p,
+                               float *features_dev, float *workspace_dev, int64_t workspace_words, void *stream) {
+    if (!tokens_dev || !features_dev || !mission_params_ok(p))
+        return fail(MGX_ERR_INVALID, "mgx_mission_forward: null pointer");
+    const int64_t need = mgx_mission_workspace_words(n_rows, seq_len);
+    if (need < 0) return fail(MGX_ERR_INVALID, "mgx_mission_forward: n_rows must be in 1..2048, seq_len in 1..256");
+    if (workspace_dev && workspace_words < need)
+        return fail(MGX_ERR_INVALID, "mgx_mission_forward: workspace_words below mgx_mission_workspace_words");
+    MissionArgs a;
+    a.tokens = tokens_dev; a.n_rows = n_rows; a.T = seq_len;
+    a.emb = p->embedding_dev; a.w_ih = p->w_ih_dev; a.w_hh = p->w_hh_dev; a.b_ih = p->b_ih_dev; a.b_hh = p->b_hh_dev;
+    a.feat = features_dev; a.g_feat = nullptr; a.ws = workspace_dev;
+    const unsigned nblk = (unsigned)((n_rows + MS_ROWS - 1) / MS_ROWS);
+    hipLaunchKernelGGL(mgx_mission_forward_kernel, dim3(nblk), dim3(MS_THREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return MGX_OK;
+}
+
+mgx_status mgx_mission_backward(const uint8_t *tokens_dev, int64_t n_rows, int seq_len, const mgx_mission_params *p,
+                                const float *g_features_dev, float *workspace_dev, int64_t workspace_words,
+                                const mgx_mission_grads *g, void *stream) {
+    if (!tokens_dev || !g_features_dev || !workspace_dev || !mission_params_ok(p) || !g || !g->embedding_dev ||
+        !g->w_ih_dev || !g->w_hh_dev || !g->b_ih_dev || !g->b_hh_dev)
+        return fail(MGX_ERR_INVALID, "mgx_mission_backward: null pointer");
+    const int64_t need = mgx_mission_workspace_words(n_rows, seq_len);
+    if (need < 0) return fail(MGX_ERR_INVALID, "mgx_mission_backward: n_rows must be in 1..2048, seq_len in 1..256");
+    if (workspace_words < need)
+        return fail(MGX_ERR_INVALID, "mgx_mission_backward: workspace_words below mgx_mission_workspace_words");
+    const int64_t pairs = n_rows * seq_len;
+    const int chunks = mission_chunks(pairs);
+    MissionArgs a;
+    a.tokens = tokens_dev; a.n_rows = n_rows; a.T = seq_len;
+    a.emb = p->embedding_dev; a.w_ih = p->w_ih_dev; a.w_hh = p->w_hh_dev; a.b_ih = p->b_ih_dev; a.b_hh = p->b_hh_dev;
+    a.feat = nullptr; a.g_feat = g_features_dev; a.ws = workspace_dev;
+    const unsigned nblk = (unsigned)((n_rows + MS_ROWS - 1) / MS_ROWS);
+    hipLaunchKernelGGL(mgx_mission_bptt_kernel, dim3(nblk), dim3(MS_THREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    MissionWArgs w;
+    w.tokens = tokens_dev; w.ws = workspace_dev; w.K = (int)pairs; w.T = seq_len;
+    w.L = (int)((pairs + chunks - 1) / chunks);
+    w.L += w.L & 1;
+    w.part = workspace_dev + pairs * MS_REC;
+    float *dG = w.part + (int64_t)chunks * MS_SLAB;
+    hipLaunchKernelGGL(mgx_mission_wgrad_kernel, dim3(MS_G / 32, (unsigned)chunks), dim3(MS_THREADS), 0,
+                       (hipStream_t)stream, w);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mgx_mission_fold_kernel, dim3((MS_SLAB + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                       (const float *)w.part, chunks, g->w_hh_dev, dG, g->b_hh_dev);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mgx_mission_input_grad_kernel, dim3((MS_INPUT_GRAD_OUTPUTS + 7) / 8), dim3(256), 0,
+                       (hipStream_t)stream, (const float *)dG, p->embedding_dev, p->w_ih_dev, g->embedding_dev,
+                       g->w_ih_dev, g->b_ih_dev, g->b_hh_dev);
     HIP_TRY(hipGetLastError());
     return MGX_OK;
 }

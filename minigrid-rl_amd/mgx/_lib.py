@@ -28,7 +28,8 @@ EXPORTS = ("mgx_last_error", "mgx_abi_version", "mgx_create", "mgx_destroy", "mg
            "mgx_step_compact", "mgx_rollout_compact", "mgx_rollout_compact_gae", "mgx_observe_compact", "mgx_gather",
            "mgx_gather_ring", "mgx_scene", "mgx_set_clock", "mgx_clock_words", "mgx_clock_groups",
            "mgx_ring_levels", "mgx_random_actions", "mgx_set_random_policy", "mgx_policy_blob_words",
-           "mgx_policy_act", "mgx_policy_grad_scratch_words", "mgx_policy_backward")
+           "mgx_policy_act", "mgx_policy_grad_scratch_words", "mgx_policy_backward",
+           "mgx_mission_workspace_words", "mgx_mission_forward", "mgx_mission_backward")
 CLOCK_CLASSES = 4   # == MGX_CLOCK_CLASSES (include/mgx.h)
 
 
@@ -108,6 +109,15 @@ class MgxPolicyGrad(ctypes.Structure):
     ]
 
 
+class MgxMissionParams(ctypes.Structure):
+    _fields_ = [("embedding_dev", ctypes.c_void_p), ("w_ih_dev", ctypes.c_void_p), ("w_hh_dev", ctypes.c_void_p),
+                ("b_ih_dev", ctypes.c_void_p), ("b_hh_dev", ctypes.c_void_p)]
+
+
+class MgxMissionGrads(ctypes.Structure):
+    _fields_ = MgxMissionParams._fields_
+
+
 class MgxError(RuntimeError):
     pass
 
@@ -156,6 +166,11 @@ def load():
     L.mgx_policy_grad_scratch_words.argtypes = [I, I64, I]
     L.mgx_policy_grad_scratch_words.restype = I64
     L.mgx_policy_backward.argtypes = [P, P, P, P, I64, I64, P, I64, ctypes.POINTER(MgxPolicyGrad), P]
+    L.mgx_mission_workspace_words.argtypes = [I64, I]
+    L.mgx_mission_workspace_words.restype = I64
+    L.mgx_mission_forward.argtypes = [P, I64, I, ctypes.POINTER(MgxMissionParams), P, P, I64, P]
+    L.mgx_mission_backward.argtypes = [P, I64, I, ctypes.POINTER(MgxMissionParams), P, P, I64,
+                                       ctypes.POINTER(MgxMissionGrads), P]
     L.mgx_set_clock.argtypes = [P, P, I, ctypes.POINTER(I)]
     L.mgx_clock_words.argtypes = [P, I]
     L.mgx_clock_words.restype = I64

@@ -137,7 +137,7 @@ def mission_table(policy, tokens=None):
 class FusedActor:
     """actions / values / log-probs of `policy` for observations of a CompactBuffer of `engine`, one launch each."""
 
-    def __init__(self, policy, engine, seed=0):
+    def __init__(self, policy, engine, seed=0, fused_mission=False):
         k, _ = _params(policy)                       # ValueError before anything touches the device
         if engine is None or k != engine.n_stack:
             raise ValueError("policy n_stack %d does not match the engine's" % k)
@@ -152,6 +152,11 @@ class FusedActor:
         self.mission_feat = torch.zeros((256, k, 128), dtype=torch.float32, device=dev)
         self.counter = torch.zeros(2, dtype=torch.int64, device=dev)      # u64 [2] (mgx_random_actions' contract)
         self._tokens = _lib.mission_tokens()
+        self.mission = self._stacks = None
+        if fused_mission:                            # the table through mgx_mission_forward (mgx/fused_mission.py)
+            from .fused_mission import FusedMissionEncoder
+            self.mission = FusedMissionEncoder(policy, dev)
+            self._stacks = mission_token_stacks(k, self._tokens).reshape(256 * k, 32 * k).to(torch.uint8).to(dev)
         self._pol = _lib.MgxPolicy()
         self._out = _lib.MgxActOut()
         self.sync()
@@ -162,7 +167,10 @@ class FusedActor:
         was = self.policy.training
         self.policy.train(False)
         self.blob.copy_(pack_blob(self.policy))
-        self.mission_feat.copy_(mission_table(self.policy, self._tokens))
+        if self.mission is not None:
+            self.mission_feat.copy_(self.mission.encode(self._stacks).reshape(256, self.K, 128))
+        else:
+            self.mission_feat.copy_(mission_table(self.policy, self._tokens))
         self.policy.train(was)
 
     def _run(self, buf, index, mode, terminal=False, logits=False):

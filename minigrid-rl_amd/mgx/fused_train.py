@@ -26,12 +26,16 @@ def differentiable_blob(tensors):
     return torch.cat([t.to(torch.float32).reshape(-1) for t in tensors])
 
 
-def mission_table_rows(policy, rows, stacks):
+def mission_table_rows(policy, rows, stacks, encoder=None):
     """f32 [256, n_stack, 128]: fused_policy.mission_table restricted to the flat rows `rows` (i64 [r], row =
-    mid * n_stack + v - 1; `stacks` i64 [r, 32 * n_stack] their token stacks), the rest zero -- with autograd."""
+    mid * n_stack + v - 1; `stacks` i64 [r, 32 * n_stack] their token stacks), the rest zero -- with autograd.
+    With `encoder` (a FusedMissionEncoder; `stacks` then u8) the rows come from the fused mission kernels."""
     k, _ = _params(policy)
     fe = policy.features_extractor
-    out = fe._mission_chunked(fe.extractors["mission"], stacks).to(torch.float32)
+    if encoder is not None:
+        out = encoder.encode(stacks)
+    else:
+        out = fe._mission_chunked(fe.extractors["mission"], stacks).to(torch.float32)
     tab = torch.zeros((256 * k, 128), dtype=torch.float32, device=out.device)
     return tab.index_copy(0, rows, out).reshape(256, k, 128)
 
@@ -62,9 +66,10 @@ class _PolicyFn(torch.autograd.Function):
 
 class FusedEvaluator:
     """evaluate_actions of `policy` for samples of a CompactBuffer of `engine`, differentiable with respect to
-    every parameter.  max_groups: mgx_policy_grad.max_groups (0: the library's default)."""
+    every parameter.  max_groups: mgx_policy_grad.max_groups (0: the library's default).  fused_mission: the table's
+    rows come from mgx_mission_forward / mgx_mission_backward (mgx/fused_mission.py), not from MIOpen's GRU."""
 
-    def __init__(self, policy, engine, max_groups=0):
+    def __init__(self, policy, engine, max_groups=0, fused_mission=False):
         k, _ = _params(policy)                       # ValueError before anything touches the device
         if engine is None or k != engine.n_stack:
             raise ValueError("policy n_stack %d does not match the engine's" % k)
@@ -73,7 +78,13 @@ class FusedEvaluator:
         self.words = int(engine.L.mgx_policy_blob_words(k))
         if self.words != blob_words(k):
             raise _lib.MgxError("blob layout mismatch: library %d words, packer %d" % (self.words, blob_words(k)))
-        self._stacks_all = mission_token_stacks(k, _lib.mission_tokens()).reshape(256 * k, 32 * k).to(engine.device)
+        self._stacks_all = mission_token_stacks(k, _lib.mission_tokens()).reshape(256 * k, 32 * k)
+        self.mission = None
+        if fused_mission:
+            from .fused_mission import FusedMissionEncoder
+            self.mission = FusedMissionEncoder(policy, engine.device)
+            self._stacks_all = self._stacks_all.to(torch.uint8)       # the kernels read the token stacks as u8
+        self._stacks_all = self._stacks_all.to(engine.device)
         self._rows = self._stacks = None
         self._scratch = None
         self._pol, self._out, self._grad = _lib.MgxPolicy(), _lib.MgxActOut(), _lib.MgxPolicyGrad()
@@ -83,12 +94,12 @@ class FusedEvaluator:
         mids = torch.unique(buf.mids).to(torch.int64)
         k = self.K
         self._rows = (mids[:, None] * k + torch.arange(k, device=mids.device)[None, :]).reshape(-1)
-        self._stacks = self._stacks_all.index_select(0, self._rows)
+        self._stacks = self._stacks_all.index_select(0, self._rows).contiguous()
 
     def inputs(self):
         """(blob, mission_feat): the kernel's two differentiable inputs from the policy's current parameters."""
         _, tensors = _params(self.policy)
-        return differentiable_blob(tensors), mission_table_rows(self.policy, self._rows, self._stacks)
+        return differentiable_blob(tensors), mission_table_rows(self.policy, self._rows, self._stacks, self.mission)
 
     def _addr(self, buf, index):
         e = self.engine

@@ -68,7 +68,13 @@ class PPOConfig:
                                         # (mgx/fused_policy.py; own sampling stream) instead of pol(gathered obs)
     fused_train: bool = False           # compact layout: Trainer.train evaluates each minibatch through mgx_policy_act
                                         # + mgx_policy_backward (mgx/fused_train.py) instead of pol.evaluate_actions
+    fused_mission: bool = False         # with fused_act / fused_train: the mission Embedding + GRU through
+                                        # mgx_mission_forward / mgx_mission_backward (mgx/fused_mission.py)
     env: dict = field(default_factory=lambda: dict(problem="multi", mission=2, size=8, num_objects=4))
+
+    def __post_init__(self):
+        if self.fused_mission and not (self.fused_train or self.fused_act):
+            raise ValueError("fused_mission needs fused_train or fused_act")
 
 
 def linear_schedule(initial_value, final_value):
@@ -247,7 +253,7 @@ class CompactRolloutCollector:
         self.fused = None
         if getattr(cfg, "fused_act", False):
             from .fused_policy import FusedActor
-            self.fused = FusedActor(policy, engine, seed=cfg.seed)
+            self.fused = FusedActor(policy, engine, seed=cfg.seed, fused_mission=getattr(cfg, "fused_mission", False))
         n, k, dev = engine.n, engine.n_stack, engine.device
         self._obs = dict(image=torch.empty((n, 3 * k, 7, 7), dtype=torch.float32, device=dev),
                          direction=torch.empty((n, 4 * k), dtype=torch.float32, device=dev),
@@ -359,7 +365,7 @@ class Trainer:
         if getattr(cfg, "fused_train", False):
             if self.fused is None or self.fused.engine is not buf.buf.engine:
                 from .fused_train import FusedEvaluator
-                self.fused = FusedEvaluator(pol, buf.buf.engine)
+                self.fused = FusedEvaluator(pol, buf.buf.engine, fused_mission=getattr(cfg, "fused_mission", False))
             fused = self.fused
             fused.prepare(buf.buf)         # the mission ids of this rollout: the table rows each minibatch computes
         for epoch in range(cfg.n_epochs):

@@ -14,6 +14,12 @@ The two legs alternate in one loop; device events after a warm-up; median and ra
 Every part runs in a child process of its own under a time limit; the first failure ends the run.
   python tools/bench_policy_train.py [--out profiles/r10_policy_train] [--sha BUILD] [--envs 65536] [--repeats 20]
 writes OUT/train.json and OUT/parity.json.
+
+--fused-mission measures the fused mission encoder (mgx_mission_forward / mgx_mission_backward through
+mgx/fused_mission.py) instead, into profiles/r12_mission_gru: the same minibatch step with fused_train on and
+fused_mission off and on in alternation (flag off is the path above, unchanged), inputs() and its backward alone
+for both, and the per-tensor parity ratios of tests/test_fused_mission_gpu.py's yardstick on the rollout's
+(mission id, v) table rows.
 """
 import argparse
 import copy
@@ -196,17 +202,100 @@ def part_parity(args):
     return dict(samples=n, n_stack=4, tensors=out, worst_ratio=max(v["ratio"] for v in out.values()))
 
 
-PARTS = {"step": (part_step, 420), "train": (part_train, 540), "parity": (part_parity, 540)}
+def _mission_setup(args, torch):
+    """_setup's rollout and policy, and two FusedEvaluators over it: fused_mission off and on."""
+    from mgx.fused_train import FusedEvaluator
+    eng, col, ro, cfgs, pols, trainers = _setup(args, torch)
+    pol = pols[True]
+    pol.train(True)
+    evs = {f: FusedEvaluator(pol, eng, fused_mission=f) for f in (False, True)}
+    for ev in evs.values():
+        ev.prepare(ro.buf)
+    return eng, ro, cfgs[True], pol, evs
+
+
+def part_mission_step(args):
+    import torch
+    eng, ro, cfg, pol, evs = _mission_setup(args, torch)
+    perm = torch.randperm(ro.T * ro.N, device=eng.device)
+    index, actions, old_v, old_lp, adv, ret = next(ro.minibatch_indices(cfg.batch_size, perm))
+    adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+
+    def step(f):
+        values, log_prob, entropy = evs[f].evaluate_actions(ro.buf, index, actions)
+        ratio = torch.exp(log_prob - old_lp)
+        policy_loss = -torch.min(adv * ratio, adv * torch.clamp(ratio, 1 - cfg.clip_range, 1 + cfg.clip_range)).mean()
+        vp = old_v + torch.clamp(values - old_v, -cfg.clip_range_vf, cfg.clip_range_vf)
+        loss = policy_loss - cfg.ent_coef * entropy.mean() + cfg.vf_coef * torch.nn.functional.mse_loss(ret, vp)
+        pol.optimizer.zero_grad()
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(pol.parameters(), cfg.max_grad_norm)
+        pol.optimizer.step()
+
+    def inputs(f):
+        blob, table = evs[f].inputs()
+        (table.sum() + blob.sum()).backward()
+
+    out = {}
+    for name, fn in (("step", step), ("inputs_forward_and_backward", inputs)):
+        for _ in range(3):
+            fn(False), fn(True)
+        torch.cuda.synchronize()
+        ms = {False: [], True: []}
+        for _ in range(args.repeats):
+            for f in (False, True):
+                ms[f].append(_timed(lambda: fn(f), torch))
+        off, on = _stat(ms[False]), _stat(ms[True])
+        out[name] = dict(fused_mission_off=off, fused_mission_on=on, ratio_off_over_on=off["median_ms"] / on["median_ms"],
+                         every_on_below_every_off=on["max_ms"] < off["min_ms"])
+    eng.poll_error()
+    return dict(n_envs=args.envs, rows=int(index.numel()), n_stack=4, env=ENV3, table_rows=int(evs[True]._rows.numel()),
+                seq_len=int(evs[True]._stacks.shape[1]), **out)
+
+
+def part_mission_parity(args):
+    import torch
+    import test_fused_mission_gpu as M
+    from mgx.fused_mission import mission_params
+    eng, ro, cfg, pol, evs = _mission_setup(args, torch)
+    seq32 = pol.features_extractor.extractors["mission"]
+    seq64 = copy.deepcopy(seq32).cpu().double()
+    tok = evs[True]._stacks.cpu()
+    g = torch.randn((tok.shape[0], 128), generator=torch.Generator().manual_seed(17))
+    ref = M._module(seq64, tok.long(), g)
+    t32 = M._module(seq32, tok.long().to(eng.device), g.to(eng.device))
+    c = M.Ctx()
+    c.enc, c.params = evs[True].mission, mission_params(pol)
+    got = M._kernel(c, tok, g)
+    tensors = dict(ref[1], features=ref[0])
+    t32 = dict(t32[1], features=t32[0])
+    got = dict(got[1], features=got[0])
+    out = {}
+    for name in tensors:
+        e_torch = float((t32[name] - tensors[name]).abs().max())
+        scale = float(tensors[name].abs().max())
+        bound = max(4.0 * e_torch, 4.0 * M.EPS32 * scale)
+        dev = float((got[name].double().cpu() - tensors[name]).abs().max())
+        out[name] = dict(kernel_max_abs_dev_vs_fp64=dev, torch_fp32_gpu_max_abs_dev_vs_fp64=e_torch, bound=bound,
+                         ratio=dev / bound, max_abs_ref=scale)
+        print("%s: kernel %.3e torch %.3e ratio %.2f" % (name, dev, e_torch, dev / bound))
+    return dict(table_rows=int(tok.shape[0]), seq_len=int(tok.shape[1]), tensors=out,
+                worst_ratio=max(v["ratio"] for v in out.values()))
+
+
+PARTS = {"step": (part_step, 420), "train": (part_train, 540), "parity": (part_parity, 540),
+         "mission_step": (part_mission_step, 420), "mission_parity": (part_mission_parity, 300)}
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r10_policy_train"))
+    ap.add_argument("--out", default=None, help="default: profiles/r10_policy_train (r12_mission_gru with --fused-mission)")
+    ap.add_argument("--fused-mission", action="store_true", help="measure the fused mission encoder instead")
     ap.add_argument("--sha", default=None, help="build id to record (default: git rev-parse HEAD)")
     ap.add_argument("--envs", type=int, default=65536)
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--parity-samples", type=int, default=65536)
-    ap.add_argument("--parts", default="parity,step,train")
+    ap.add_argument("--parts", default=None, help="default: parity,step,train (mission_parity,mission_step)")
     ap.add_argument("--part", choices=sorted(PARTS), default=None, help="(internal) run one part in this process")
     args = ap.parse_args()
     if args.part:
@@ -214,6 +303,10 @@ def main():
         return 0
     if args.repeats < 20:
         ap.error("--repeats must be >= 20")
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "r12_mission_gru" if args.fused_mission else "r10_policy_train")
+    if args.parts is None:
+        args.parts = "mission_parity,mission_step" if args.fused_mission else "parity,step,train"
     sha = args.sha
     if sha is None:
         try:
@@ -236,6 +329,14 @@ def main():
             return 1
         res[name] = json.loads(lines[-1][7:])
         print(name, json.dumps(res[name]))
+    if "mission_parity" in res:
+        with open(os.path.join(args.out, "parity.json"), "w") as f:
+            json.dump(dict(meta, **res["mission_parity"]), f, indent=1, sort_keys=True)
+            f.write("\n")
+    if "mission_step" in res:
+        with open(os.path.join(args.out, "train.json"), "w") as f:
+            json.dump(dict(meta, **res["mission_step"]), f, indent=1, sort_keys=True)
+            f.write("\n")
     if "parity" in res:
         with open(os.path.join(args.out, "parity.json"), "w") as f:
             json.dump(dict(meta, **res["parity"]), f, indent=1, sort_keys=True)
