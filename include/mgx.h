@@ -389,6 +389,99 @@ mgx_status mgx_mission_backward(const uint8_t *tokens_dev, int64_t n_rows, int s
                                 const float *g_features_dev, float *workspace_dev, int64_t workspace_words,
                                 const mgx_mission_grads *g, void *stream);
 
+/* ---- PPO loss: statistics and cotangents (added within ABI 9) ----------------------------------------
+ * Replaces the loss block of SB3's PPO.train (stable_baselines3/ppo/ppo.py; mgx/ppo.py Trainer.train) and its
+ * autograd graph down to the network outputs: from the logits and values mgx_policy_act (mode 0) wrote and
+ * the rollout's arrays it writes the loss statistics and dL/dlogits, dL/dvalues -- exactly what
+ * mgx_policy_backward consumes.  fp32, expf / logf; sums over samples in fp64 (below).  With p = softmax(z),
+ * lp = log p[a], H = -sum p log p, r = exp(lp - old_lp), A the (normalised) advantage, c = clip_range:
+ *    policy_loss  = -mean min(A r, A clamp(r, 1 - c, 1 + c))      value_loss = mean (ret - vp)^2
+ *    entropy_loss = -mean H        approx_kl = mean (r - 1) - log r        clip_fraction = mean [|r - 1| > c]
+ *    loss         = policy_loss + ent_coef entropy_loss + vf_coef value_loss
+ *    vp           = old_v + clamp(v - old_v, -c_v, c_v), or v when clip_range_vf <= 0
+ *    dL/dlp  = -A r / B where 1 - c <= r <= 1 + c or A r < A clamp(r), else 0
+ *    dL/dz_j = dL/dlp ([j = a] - p_j) + ent_coef / B p_j (log p_j + H)
+ *    dL/dv   = vf_coef 2 (vp - ret) / B where |v - old_v| <= c_v (or no value clipping), else 0
+ * The rollout's arrays are read at element sel_dev[i] for sample i (sel_dev NULL: element i); logits, values
+ * and the outputs are indexed by i.  Actions outside 0..6 are clamped into that range.
+ * adv_mode 0: A = advantage.  1: A = (a - mean) / (std + 1e-8) over the n_samples advantages, std unbiased as
+ * Tensor.std(); not applied when n_samples = 1 (as PPO.train).  2: mean and std read from adv_stats_dev.
+ * stats_dev f32 [8] = policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction, loss, the advantage mean
+ * and std used (0 and 1 where none were).
+ *
+ * Summation order.  ceil(n_samples / 256) workgroups, at most 256; a thread adds its samples in index order
+ * into fp64, a workgroup's threads are added by a fixed tree, the partials go to scratch_dev and the next
+ * launch adds them by the same tree.  adv_mode 1 is a pass of its own in front (the advantage sums, shifted
+ * by the first sample's).  Two or three launches, no float atomics: every output is bitwise reproducible
+ * for a given n_samples.  clip_range .. vf_coef are by-value arguments: a captured graph bakes them in. */
+int64_t mgx_ppo_loss_scratch_words(int64_t n_samples);      /* host only; -1 unless n_samples > 0 */
+
+typedef struct mgx_ppo_loss_args {
+    const float *logits_dev;        /* f32 [n_samples][7], as mgx_act_out.logits_dev */
+    const float *values_dev;        /* f32 [n_samples] */
+    const int64_t *sel_dev;         /* i64 [n_samples] or NULL: the element of the five arrays below sample i reads */
+    const int64_t *actions_dev;     /* i64 */
+    const float *old_values_dev;    /* f32, as the four below */
+    const float *old_log_probs_dev;
+    const float *advantages_dev;
+    const float *returns_dev;
+    const float *adv_stats_dev;     /* f32 [2] mean, std: adv_mode 2 only */
+    float *g_logits_dev;            /* f32 [n_samples][7]; OVERWRITTEN */
+    float *g_values_dev;            /* f32 [n_samples]; OVERWRITTEN */
+    float *stats_dev;               /* f32 [8]; OVERWRITTEN */
+    float *scratch_dev;             /* f32 [scratch_words], 8-byte aligned, caller-owned, need not be zeroed */
+    int64_t scratch_words;
+    double clip_range;              /* > 0 */
+    double clip_range_vf;           /* <= 0: no value clipping */
+    double ent_coef;
+    double vf_coef;
+    int32_t adv_mode;               /* 0 raw, 1 minibatch statistics, 2 adv_stats_dev */
+    int32_t reserved0;              /* 0 */
+} mgx_ppo_loss_args;
+
+/* Takes no engine handle.  Only enqueues on `stream` (no allocation, no host sync; capturable).
+ * MGX_ERR_INVALID before any HIP call for: a null pointer (sel_dev excepted; adv_stats_dev unless adv_mode 2),
+ * n_samples <= 0, adv_mode outside 0..2, clip_range <= 0, scratch_words below mgx_ppo_loss_scratch_words(...),
+ * a scratch that is not 8-byte aligned. */
+mgx_status mgx_ppo_loss(int64_t n_samples, const mgx_ppo_loss_args *a, void *stream);
+
+/* ---- Gradient-norm clip + Adam over one flat array (added within ABI 9) ---------------------------------
+ * Replaces torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) followed by torch.optim.Adam.step()
+ * (defaults: no weight decay, no amsgrad) for parameters, gradients and moments that each live in one flat
+ * fp32 array:
+ *    g = grad * grad_scale                (the data-parallel mean after one summing all-reduce)
+ *    total = ||g||_2,  coef = min(1, max_grad_norm / (total + 1e-6))   (1 when max_grad_norm <= 0)
+ *    grad <- g * coef                     (WRITTEN BACK: the clipped gradient stays inspectable, as p.grad)
+ *    exp_avg <- exp_avg + (1 - beta1) (grad - exp_avg),  exp_avg_sq <- beta2 exp_avg_sq + (1 - beta2) grad^2
+ *    param <- param - lr / (1 - beta1^step) * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^step) + eps)
+ * The bias corrections are formed on the host in double from `step`, as torch forms them.  lr and the
+ * corrections are therefore by-value arguments: a captured graph bakes them in, so a schedule or the next
+ * step needs a new capture (or updated kernel-node parameters).  Non-finite gradients propagate exactly as in
+ * torch (a NaN norm makes every gradient NaN); there is no special case.
+ *
+ * Summation order.  The norm is summed as mgx_ppo_loss sums: ceil(n_words / 1024) workgroups, at most 256,
+ * fp64, fixed order, partials in scratch_dev, folded by every workgroup of the second launch.  Two launches,
+ * no float atomics: bitwise reproducible for a given n_words. */
+int64_t mgx_adam_scratch_words(int64_t n_words);            /* host only; -1 unless n_words > 0 */
+
+typedef struct mgx_adam_args {
+    double lr;
+    double beta1, beta2;            /* each in [0, 1) */
+    double eps;                     /* >= 0 */
+    int64_t step;                   /* 1-based count of this step */
+    double max_grad_norm;           /* <= 0: no clip */
+    double grad_scale;              /* 1: none */
+} mgx_adam_args;
+
+/* param_dev .. exp_avg_sq_dev f32 [n_words], caller-owned, each updated in place.  total_norm_dev: optional
+ * f32 [1], the norm before the clip.  scratch_dev f32 [scratch_words], 8-byte aligned, need not be zeroed.
+ * Only enqueues on `stream` (no allocation, no host sync; capturable).  MGX_ERR_INVALID before any HIP call
+ * for: a null pointer (total_norm_dev excepted), n_words <= 0, step < 1, a beta outside [0, 1), eps < 0,
+ * scratch_words below mgx_adam_scratch_words(n_words), a scratch that is not 8-byte aligned. */
+mgx_status mgx_adam_step(float *param_dev, float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev,
+                         int64_t n_words, const mgx_adam_args *a, float *total_norm_dev, float *scratch_dev,
+                         int64_t scratch_words, void *stream);
+
 /* Makes `stream` wait for the in-flight refill, if any (no host sync). */
 mgx_status mgx_join(mgx_handle *h, void *stream);
 

@@ -2730,6 +2730,7 @@ __global__ __launch_bounds__(256) void mgx_gather_kernel(const uint8_t *__restri
 #include "mgx_policy.h"   // mgx_policy_act's kernel (fused actor-critic forward over compact rows)
 #include "mgx_policy_grad.h"   // mgx_policy_backward's kernels (its gradient)
 #include "mgx_mission.h"   // mgx_mission_forward / mgx_mission_backward: the mission Embedding + GRU
+#include "mgx_update.h"    // mgx_ppo_loss / mgx_adam_step: the PPO loss and the clip + Adam step
 
 // ================================================================== host side
 thread_local std::string g_last_error;
@@ -3969,6 +3970,90 @@ mgx_status mgx_mission_backward(const uint8_t *tokens_dev, int64_t n_rows, int s
     hipLaunchKernelGGL(mgx_mission_input_grad_kernel, dim3((MS_INPUT_GRAD_OUTPUTS + 7) / 8), dim3(256), 0,
                        (hipStream_t)stream, (const float *)dG, p->embedding_dev, p->w_ih_dev, g->embedding_dev,
                        g->w_ih_dev, g->b_ih_dev, g->b_hh_dev);
+    HIP_TRY(hipGetLastError());
+    return MGX_OK;
+}
+
+// ---- PPO loss and clip + Adam (mgx_update.h): no engine handle
+static int update_groups(int64_t n, int per_group) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(UP_MAX_GROUPS, (n + per_group - 1) / per_group));
+}
+
+int64_t mgx_ppo_loss_scratch_words(int64_t n_samples) {
+    if (n_samples <= 0) return -1;
+    return (int64_t)update_groups(n_samples, UP_LOSS_PER_GROUP) * (2 + UP_STATS) * 2;      // doubles, in f32 words
+}
+
+int64_t mgx_adam_scratch_words(int64_t n_words) {
+    if (n_words <= 0) return -1;
+    return (int64_t)update_groups(n_words, UP_ADAM_PER_GROUP) * 2;
+}
+
+mgx_status mgx_ppo_loss(int64_t n_samples, const mgx_ppo_loss_args *p, void *stream) {
+    if (!p || !p->logits_dev || !p->values_dev || !p->actions_dev || !p->old_values_dev || !p->old_log_probs_dev ||
+        !p->advantages_dev || !p->returns_dev || !p->g_logits_dev || !p->g_values_dev || !p->stats_dev ||
+        !p->scratch_dev)
+        return fail(MGX_ERR_INVALID, "mgx_ppo_loss: null pointer");
+    if (n_samples <= 0) return fail(MGX_ERR_INVALID, "mgx_ppo_loss: n_samples must be positive");
+    if (p->adv_mode < 0 || p->adv_mode > 2) return fail(MGX_ERR_INVALID, "mgx_ppo_loss: adv_mode must be 0, 1 or 2");
+    if (p->adv_mode == 2 && !p->adv_stats_dev)
+        return fail(MGX_ERR_INVALID, "mgx_ppo_loss: adv_mode 2 needs adv_stats_dev");
+    if (!(p->clip_range > 0.0)) return fail(MGX_ERR_INVALID, "mgx_ppo_loss: clip_range must be positive");
+    if (p->scratch_words < mgx_ppo_loss_scratch_words(n_samples))
+        return fail(MGX_ERR_INVALID, "mgx_ppo_loss: scratch_words below mgx_ppo_loss_scratch_words");
+    if ((uintptr_t)p->scratch_dev & 7) return fail(MGX_ERR_INVALID, "mgx_ppo_loss: scratch_dev must be 8-byte aligned");
+    PpoLossArgs a;
+    a.logits = p->logits_dev; a.values = p->values_dev; a.sel = p->sel_dev; a.actions = p->actions_dev;
+    a.old_values = p->old_values_dev; a.old_log_probs = p->old_log_probs_dev; a.advantages = p->advantages_dev;
+    a.returns = p->returns_dev; a.adv_stats = p->adv_stats_dev;
+    a.g_logits = p->g_logits_dev; a.g_values = p->g_values_dev; a.stats = p->stats_dev;
+    a.B = n_samples;
+    a.groups = update_groups(n_samples, UP_LOSS_PER_GROUP);
+    a.adv_part = (double *)p->scratch_dev;
+    a.stat_part = a.adv_part + 2 * a.groups;
+    a.adv_mode = (p->adv_mode == 1 && n_samples == 1) ? 0 : p->adv_mode;       // as PPO.train: no std of one sample
+    a.lo = (float)(1.0 - p->clip_range); a.hi = (float)(1.0 + p->clip_range); a.clip = (float)p->clip_range;
+    a.clip_vf = p->clip_range_vf > 0.0 ? (float)p->clip_range_vf : 0.f;
+    a.ent_coef = (float)p->ent_coef; a.vf_coef = (float)p->vf_coef;
+    a.inv_b = 1.f / (float)n_samples;
+    if (a.adv_mode == 1) {
+        hipLaunchKernelGGL(mgx_ppo_adv_kernel, dim3((unsigned)a.groups), dim3(UP_THREADS), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(mgx_ppo_loss_kernel, dim3((unsigned)a.groups), dim3(UP_THREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mgx_ppo_stats_kernel, dim3(1), dim3(UP_THREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return MGX_OK;
+}
+
+mgx_status mgx_adam_step(float *param_dev, float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev,
+                         int64_t n_words, const mgx_adam_args *p, float *total_norm_dev, float *scratch_dev,
+                         int64_t scratch_words, void *stream) {
+    if (!param_dev || !grad_dev || !exp_avg_dev || !exp_avg_sq_dev || !p || !scratch_dev)
+        return fail(MGX_ERR_INVALID, "mgx_adam_step: null pointer");
+    if (n_words <= 0) return fail(MGX_ERR_INVALID, "mgx_adam_step: n_words must be positive");
+    if (p->step < 1) return fail(MGX_ERR_INVALID, "mgx_adam_step: step counts from 1");
+    if (!(p->beta1 >= 0.0 && p->beta1 < 1.0) || !(p->beta2 >= 0.0 && p->beta2 < 1.0))
+        return fail(MGX_ERR_INVALID, "mgx_adam_step: betas must be in [0, 1)");
+    if (!(p->eps >= 0.0)) return fail(MGX_ERR_INVALID, "mgx_adam_step: eps must not be negative");
+    if (scratch_words < mgx_adam_scratch_words(n_words))
+        return fail(MGX_ERR_INVALID, "mgx_adam_step: scratch_words below mgx_adam_scratch_words");
+    if ((uintptr_t)scratch_dev & 7) return fail(MGX_ERR_INVALID, "mgx_adam_step: scratch_dev must be 8-byte aligned");
+    AdamArgs a;
+    a.param = param_dev; a.grad = grad_dev; a.exp_avg = exp_avg_dev; a.exp_avg_sq = exp_avg_sq_dev;
+    a.norm_out = total_norm_dev; a.part = (double *)scratch_dev;
+    a.n = n_words;
+    a.groups = update_groups(n_words, UP_ADAM_PER_GROUP);
+    a.grad_scale = (float)p->grad_scale;
+    a.max_norm = p->max_grad_norm > 0.0 ? (float)p->max_grad_norm : 0.f;
+    // torch.optim.Adam (_single_tensor_adam): the corrections in double from the step count, cast where they meet fp32
+    const double bc1 = 1.0 - std::pow(p->beta1, (double)p->step), bc2 = 1.0 - std::pow(p->beta2, (double)p->step);
+    a.w1 = (float)(1.0 - p->beta1); a.beta2 = (float)p->beta2; a.w2 = (float)(1.0 - p->beta2);
+    a.step_size = (float)(p->lr / bc1); a.bc2_sqrt = (float)std::sqrt(bc2); a.eps = (float)p->eps;
+    hipLaunchKernelGGL(mgx_adam_norm_kernel, dim3((unsigned)a.groups), dim3(UP_THREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mgx_adam_step_kernel, dim3((unsigned)a.groups), dim3(UP_THREADS), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return MGX_OK;
 }

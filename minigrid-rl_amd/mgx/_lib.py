@@ -29,7 +29,8 @@ EXPORTS = ("mgx_last_error", "mgx_abi_version", "mgx_create", "mgx_destroy", "mg
            "mgx_gather_ring", "mgx_scene", "mgx_set_clock", "mgx_clock_words", "mgx_clock_groups",
            "mgx_ring_levels", "mgx_random_actions", "mgx_set_random_policy", "mgx_policy_blob_words",
            "mgx_policy_act", "mgx_policy_grad_scratch_words", "mgx_policy_backward",
-           "mgx_mission_workspace_words", "mgx_mission_forward", "mgx_mission_backward")
+           "mgx_mission_workspace_words", "mgx_mission_forward", "mgx_mission_backward",
+           "mgx_ppo_loss_scratch_words", "mgx_ppo_loss", "mgx_adam_scratch_words", "mgx_adam_step")
 CLOCK_CLASSES = 4   # == MGX_CLOCK_CLASSES (include/mgx.h)
 
 
@@ -118,6 +119,25 @@ class MgxMissionGrads(ctypes.Structure):
     _fields_ = MgxMissionParams._fields_
 
 
+class MgxPpoLossArgs(ctypes.Structure):
+    _fields_ = [
+        ("logits_dev", ctypes.c_void_p), ("values_dev", ctypes.c_void_p), ("sel_dev", ctypes.c_void_p),
+        ("actions_dev", ctypes.c_void_p), ("old_values_dev", ctypes.c_void_p), ("old_log_probs_dev", ctypes.c_void_p),
+        ("advantages_dev", ctypes.c_void_p), ("returns_dev", ctypes.c_void_p), ("adv_stats_dev", ctypes.c_void_p),
+        ("g_logits_dev", ctypes.c_void_p), ("g_values_dev", ctypes.c_void_p), ("stats_dev", ctypes.c_void_p),
+        ("scratch_dev", ctypes.c_void_p), ("scratch_words", ctypes.c_int64),
+        ("clip_range", ctypes.c_double), ("clip_range_vf", ctypes.c_double), ("ent_coef", ctypes.c_double),
+        ("vf_coef", ctypes.c_double), ("adv_mode", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+    ]
+
+
+class MgxAdamArgs(ctypes.Structure):
+    _fields_ = [
+        ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+        ("step", ctypes.c_int64), ("max_grad_norm", ctypes.c_double), ("grad_scale", ctypes.c_double),
+    ]
+
+
 class MgxError(RuntimeError):
     pass
 
@@ -171,6 +191,12 @@ def load():
     L.mgx_mission_forward.argtypes = [P, I64, I, ctypes.POINTER(MgxMissionParams), P, P, I64, P]
     L.mgx_mission_backward.argtypes = [P, I64, I, ctypes.POINTER(MgxMissionParams), P, P, I64,
                                        ctypes.POINTER(MgxMissionGrads), P]
+    L.mgx_ppo_loss_scratch_words.argtypes = [I64]
+    L.mgx_ppo_loss_scratch_words.restype = I64
+    L.mgx_ppo_loss.argtypes = [I64, ctypes.POINTER(MgxPpoLossArgs), P]
+    L.mgx_adam_scratch_words.argtypes = [I64]
+    L.mgx_adam_scratch_words.restype = I64
+    L.mgx_adam_step.argtypes = [P, P, P, P, I64, ctypes.POINTER(MgxAdamArgs), P, P, I64, P]
     L.mgx_set_clock.argtypes = [P, P, I, ctypes.POINTER(I)]
     L.mgx_clock_words.argtypes = [P, I]
     L.mgx_clock_words.restype = I64

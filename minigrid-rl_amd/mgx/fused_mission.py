@@ -105,11 +105,18 @@ class FusedMissionEncoder:
                    "mgx_mission_forward")
         return feat
 
-    def backward_raw(self, tokens, params, g_features, workspace):
-        """mgx_mission_backward -> the five gradients, shaped as params; `workspace` as forward_raw left it."""
+    def backward_raw(self, tokens, params, g_features, workspace, out=None):
+        """mgx_mission_backward -> the five gradients, shaped as params; `workspace` as forward_raw left it.
+        out: five contiguous f32 tensors of those shapes to write into (mgx/fused_update.py)."""
         n, t = self._check_tokens(tokens)
         g = g_features.to(torch.float32).contiguous()
-        grads = tuple(torch.empty_like(p) for p in params)
+        if out is None:
+            grads = tuple(torch.empty_like(p) for p in params)
+        else:
+            grads = tuple(out)
+            if len(grads) != 5 or any(o.dtype != torch.float32 or not o.is_contiguous() or o.shape != p.shape or
+                                      o.device != p.device for o, p in zip(grads, params)):
+                raise ValueError("out must be five contiguous f32 tensors shaped as params")
         self._fill(self._p, params)
         self._fill(self._g, grads)
         P = ctypes.c_void_p

@@ -7,7 +7,8 @@ on the compact rows in place, the backward is mgx_policy_backward, both inside o
 torch.autograd.Function whose inputs are the packed weight blob and the mission-feature table.  Both
 inputs are built differentiably -- the blob as torch.cat of the parameters in blob_layout order, the
 table by the policy's own Embedding + GRU -- so autograd delivers p.grad for every parameter, Embedding
-and GRU included.  The Categorical on the logits, the loss, the clipping and Adam stay in torch.
+and GRU included.  The Categorical on the logits, the loss, the clipping and Adam stay in torch (mgx/fused_update.py
+replaces them too, and the autograd graph with them, on the raw calls below).
 
 The table is computed only for the mission ids that occur in the buffer (prepare(), once per train()
 call); the other rows stay zero and are never read for a sample.  The blob and the table are rebuilt
@@ -122,8 +123,9 @@ class FusedEvaluator:
                    "mgx_policy_act")
         return logits, values
 
-    def backward_raw(self, buf, index, blob, mission_feat, g_logits, g_values, scratch=None):
-        """mgx_policy_backward -> (grad_blob f32 [words], grad_mission_feat f32 [256, n_stack, 128])."""
+    def backward_raw(self, buf, index, blob, mission_feat, g_logits, g_values, scratch=None, out=None):
+        """mgx_policy_backward -> (grad_blob f32 [words], grad_mission_feat f32 [256, n_stack, 128]); out: that pair
+        as contiguous f32 tensors to write into (mgx/fused_update.py: a slice of the gradient arena)."""
         e, n, k = self.engine, index.numel(), self.K
         need = int(e.L.mgx_policy_grad_scratch_words(k, n, self.max_groups))
         if scratch is None:
@@ -132,8 +134,15 @@ class FusedEvaluator:
             scratch = self._scratch
         gl = g_logits.to(torch.float32).contiguous()
         gv = g_values.to(torch.float32).contiguous()
-        gb = torch.empty(self.words, dtype=torch.float32, device=e.device)
-        gm = torch.empty((256, k, 128), dtype=torch.float32, device=e.device)
+        if out is None:
+            gb = torch.empty(self.words, dtype=torch.float32, device=e.device)
+            gm = torch.empty((256, k, 128), dtype=torch.float32, device=e.device)
+        else:
+            gb, gm = out
+            for t, numel in ((gb, self.words), (gm, 256 * k * 128)):
+                if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel or t.device != e.device:
+                    raise ValueError("out must be contiguous f32 tensors of %d and %d elements on %s"
+                                     % (self.words, 256 * k * 128, e.device))
         g = self._grad
         g.blob_dev, g.mission_feat_dev = blob.data_ptr(), mission_feat.data_ptr()
         g.g_logits_dev, g.g_values_dev = gl.data_ptr(), gv.data_ptr()

@@ -71,10 +71,15 @@ class PPOConfig:
     fused_mission: bool = False         # with fused_act / fused_train: the mission Embedding + GRU through
                                         # mgx_mission_forward / mgx_mission_backward (mgx/fused_mission.py)
     env: dict = field(default_factory=lambda: dict(problem="multi", mission=2, size=8, num_objects=4))
+    fused_update: bool = False          # with fused_train + fused_mission: loss, gradient clip and Adam through
+                                        # mgx_ppo_loss / mgx_adam_step on one flat parameter arena, no autograd
+                                        # (mgx/fused_update.py)
 
     def __post_init__(self):
         if self.fused_mission and not (self.fused_train or self.fused_act):
             raise ValueError("fused_mission needs fused_train or fused_act")
+        if self.fused_update and not (self.fused_train and self.fused_mission and self.layout == "compact"):
+            raise ValueError("fused_update needs fused_train, fused_mission and layout='compact'")
 
 
 def linear_schedule(initial_value, final_value):
@@ -324,6 +329,7 @@ class Trainer:
         self.gen.manual_seed(cfg.seed)
         self.world = torch.distributed.get_world_size(group) if group is not None else 1
         self.fused = None              # FusedEvaluator of the rollout's engine (cfg.fused_train), made on first use
+        self.update = None             # FusedUpdate of the rollout's engine (cfg.fused_update), made on first use
         if getattr(cfg, "fused_train", False) and cfg.layout != "compact":
             raise ValueError("fused_train needs layout='compact'")
 
@@ -360,6 +366,8 @@ class Trainer:
         if cfg.adv_norm == "global":
             g_mean, g_std, _ = self.global_adv_stats(buf)
         n = buf.T * buf.N
+        if getattr(cfg, "fused_update", False):
+            return self._train_fused_update(buf, lr, g_mean, g_std, perm_fn)
         stats = dict(pg=[], vf=[], ent=[], kl=[], clipfrac=[])
         fused = None
         if getattr(cfg, "fused_train", False):
@@ -402,6 +410,38 @@ class Trainer:
                 torch.nn.utils.clip_grad_norm_(pol.parameters(), cfg.max_grad_norm)
                 pol.optimizer.step()
         return {k: float(torch.stack(v).mean()) for k, v in stats.items()} | {"lr": lr}
+
+    def _train_fused_update(self, buf, lr, g_mean, g_std, perm_fn):
+        """train() with cfg.fused_update: every minibatch is FusedUpdate.step (mgx/fused_update.py) -- kernel
+        launches from the compact rows to the updated weights, no autograd graph; the statistics of all minibatches
+        stay in one device buffer that is read once."""
+        cfg = self.cfg
+        eng = buf.buf.engine
+        if self.update is None or self.update.engine is not eng:
+            from .fused_update import FusedUpdate
+            self.update = FusedUpdate(self.policy, eng)
+        up = self.update
+        up.prepare(buf.buf)
+        T, N, bs = buf.T, buf.N, cfg.batch_size
+        rollout = (buf.actions, buf.values, buf.log_probs, buf.advantages, buf.returns)
+        mode, adv_stats = (1 if cfg.normalize_advantage else 0), None
+        if mode and g_mean is not None:                 # adv_norm="global": the statistics stay on the device
+            mode, adv_stats = 2, torch.stack([g_mean, g_std]).float()
+        rows = []
+        for epoch in range(cfg.n_epochs):
+            perm = perm_fn(T * N) if perm_fn else torch.randperm(T * N, generator=self.gen, device=self.gen.device)
+            env, t = perm // T, perm % T
+            index = buf.buf.index(t, env).to(torch.int64).contiguous()
+            sel = (t * N + env).contiguous()            # the sample's element of the [T, N] rollout arrays
+            stats = torch.zeros(((perm.numel() + bs - 1) // bs, 8), dtype=torch.float32, device=eng.device)
+            for i, s in enumerate(range(0, perm.numel(), bs)):
+                m = min(bs, perm.numel() - s)
+                up.step(buf.buf, index[s:s + m], sel[s:s + m], rollout, cfg, lr, stats[i],
+                        adv_mode=mode if m > 1 else 0, adv_stats=adv_stats, group=self.group)
+            rows.append(stats)
+        up.arena.export_state()
+        st = torch.cat(rows).mean(0).tolist()           # the one host read
+        return dict(pg=st[0], vf=st[1], ent=st[2], kl=st[3], clipfrac=st[4], lr=lr)
 
 
 def make_collector(engine, policy, cfg):

@@ -20,6 +20,12 @@ mgx/fused_mission.py) instead, into profiles/r12_mission_gru: the same minibatch
 fused_mission off and on in alternation (flag off is the path above, unchanged), inputs() and its backward alone
 for both, and the per-tensor parity ratios of tests/test_fused_mission_gpu.py's yardstick on the rollout's
 (mission id, v) table rows.
+
+--fused-update measures the fused PPO update (mgx_ppo_loss / mgx_adam_step on a flat parameter arena through
+mgx/fused_update.py) instead, into profiles/r13_ppo_update: the same minibatch step with fused_train and fused_mission
+on and fused_update off and on in alternation (flag off is the path above, unchanged), the pieces of the on-step
+each on its own, one whole Trainer.train (4 epochs x 16 minibatches) off and on, and the parity ratios of
+tests/test_fused_update_gpu.py's yardstick at the minibatch's and the arena's size.
 """
 import argparse
 import copy
@@ -283,14 +289,174 @@ def part_mission_parity(args):
                 worst_ratio=max(v["ratio"] for v in out.values()))
 
 
+def _update_setup(args, torch):
+    """_setup's rollout and two (policy, Trainer) pairs of the same initial weights, fused_train + fused_mission on
+    both: fused_update off (the path above, unchanged) and on."""
+    import dataclasses
+    from mgx.ppo import Trainer
+    eng, col, ro, cfgs, pols, _ = _setup(args, torch)
+    base = dataclasses.replace(cfgs[True], fused_mission=True)
+    cfgs = {False: base, True: dataclasses.replace(base, fused_update=True)}
+    trainers = {f: Trainer(pols[f], cfgs[f]) for f in pols}
+    return eng, ro, cfgs, pols, trainers
+
+
+def part_update_step(args):
+    import torch
+    from mgx.fused_train import FusedEvaluator
+    from mgx.fused_update import FusedUpdate, adam_step, ppo_loss
+    eng, ro, cfgs, pols, trainers = _update_setup(args, torch)
+    cfg = cfgs[True]
+    clip, clip_vf = cfg.clip_range, cfg.clip_range_vf
+    perm = torch.randperm(ro.T * ro.N, device=eng.device)[:cfg.batch_size]
+    index, actions, old_v, old_lp, adv0, ret = next(ro.minibatch_indices(cfg.batch_size, perm))
+    index = index.to(torch.int64).contiguous()
+    env, t = perm // ro.T, perm % ro.T
+    sel = (t * ro.N + env).contiguous()
+    rollout = (ro.actions, ro.values, ro.log_probs, ro.advantages, ro.returns)
+    rows = int(index.numel())
+    ev = FusedEvaluator(pols[False], eng, fused_mission=True)
+    ev.prepare(ro.buf)
+    up = FusedUpdate(pols[True], eng)
+    up.prepare(ro.buf)
+    stats_row = torch.zeros(8, device=eng.device)
+    stats = dict(pg=[], vf=[], ent=[], kl=[], clipfrac=[])
+
+    def off():                         # Trainer.train's loop body with fused_train + fused_mission, line for line
+        pol = pols[False]
+        values, log_prob, entropy = ev.evaluate_actions(ro.buf, index, actions)
+        adv = (adv0 - adv0.mean()) / (adv0.std() + 1e-8)
+        ratio = torch.exp(log_prob - old_lp)
+        pl1 = adv * ratio
+        pl2 = adv * torch.clamp(ratio, 1 - clip, 1 + clip)
+        policy_loss = -torch.min(pl1, pl2).mean()
+        values_pred = old_v + torch.clamp(values - old_v, -clip_vf, clip_vf)
+        value_loss = torch.nn.functional.mse_loss(ret, values_pred)
+        entropy_loss = -torch.mean(entropy)
+        loss = policy_loss + cfg.ent_coef * entropy_loss + cfg.vf_coef * value_loss
+        with torch.no_grad():
+            log_ratio = log_prob - old_lp
+            stats["kl"] = [torch.mean((torch.exp(log_ratio) - 1) - log_ratio)]
+            stats["clipfrac"] = [torch.mean((torch.abs(ratio - 1) > clip).float())]
+        stats["pg"], stats["vf"], stats["ent"] = [policy_loss.detach()], [value_loss.detach()], [entropy_loss.detach()]
+        pol.optimizer.zero_grad()
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(pol.parameters(), cfg.max_grad_norm)
+        pol.optimizer.step()
+
+    def on():
+        up.step(ro.buf, index, sel, rollout, cfg, 3e-4, stats_row, adv_mode=1)
+
+    for p in pols.values():
+        p.train(True)
+    for _ in range(3):
+        off(), on()
+    torch.cuda.synchronize()
+    ms = {False: [], True: []}
+    for _ in range(args.repeats):
+        ms[False].append(_timed(off, torch))
+        ms[True].append(_timed(on, torch))
+    # the on-step's pieces, each on its own
+    a, enc = up.arena, up.ev.mission
+    stacks, trows = up.ev._stacks, up.ev._rows
+    ws = enc._workspace(stacks.shape[0], stacks.shape[1])
+    logits, values = up.ev.forward_raw(ro.buf, index, up._blob, up.table)
+    g_logits, g_values = torch.empty_like(logits), torch.empty_like(values)
+    state = dict(step=a.step)
+
+    def mission_forward():
+        up.table.index_copy_(0, trows, enc.forward_raw(stacks, up._mission, ws))
+
+    def mission_backward():
+        enc.backward_raw(stacks, up._mission, up.g_table.view(-1, 128).index_select(0, trows), ws, out=up._g_mission)
+
+    def adam():
+        state["step"] += 1
+        adam_step(a.param, a.grad, a.exp_avg, a.exp_avg_sq, 3e-4, state["step"], eps=cfg.optim_eps,
+                  max_grad_norm=cfg.max_grad_norm, scratch=up._adam_scratch)
+
+    pieces = dict(
+        mission_forward_and_table=mission_forward,
+        forward_kernel=lambda: up.ev.forward_raw(ro.buf, index, up._blob, up.table),
+        ppo_loss=lambda: ppo_loss(logits, values, *rollout, clip, clip_vf, cfg.ent_coef, cfg.vf_coef, adv_mode=1, sel=sel,
+                                  out=(g_logits, g_values, stats_row), scratch=up._loss_scratch),
+        backward_kernels=lambda: up.ev.backward_raw(ro.buf, index, up._blob, up.table, g_logits, g_values,
+                                                    out=(up._g_blob, up.g_table)),
+        # the backward consumes the forward's records: the pair is timed
+        mission_forward_and_backward=lambda: (mission_forward(), mission_backward()), adam_step=adam)
+    out = {}
+    for name, fn in pieces.items():
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        out[name] = _stat([_timed(fn, torch) for _ in range(args.repeats)])
+    eng.poll_error()
+    s_off, s_on = _stat(ms[False]), _stat(ms[True])
+    return dict(n_envs=args.envs, rows=rows, n_stack=4, env=ENV3, table_rows=int(trows.numel()), arena_words=a.words,
+                off_leg="Trainer.train's loop body, fused_train + fused_mission, on a pre-indexed minibatch",
+                step_fused_update_off=s_off, step_fused_update_on=s_on,
+                ranges_overlap=not (s_on["max_ms"] < s_off["min_ms"]),
+                on_median_below_off_median=s_on["median_ms"] < s_off["median_ms"],
+                ratio_off_over_on=s_off["median_ms"] / s_on["median_ms"], on_pieces=out)
+
+
+def part_update_train(args):
+    import torch
+    eng, ro, cfgs, pols, trainers = _update_setup(args, torch)
+    for f in (False, True):
+        trainers[f].train(ro, 1.0)
+    torch.cuda.synchronize()
+    ms = {False: [], True: []}
+    for _ in range(args.repeats):
+        for f in (False, True):
+            ms[f].append(_timed(lambda: trainers[f].train(ro, 1.0), torch))
+    eng.poll_error()
+    off, on = _stat(ms[False]), _stat(ms[True])
+    cfg = cfgs[True]
+    return dict(n_envs=args.envs, horizon=16, n_epochs=cfg.n_epochs, batch_size=cfg.batch_size,
+                minibatches=cfg.n_epochs * ((args.envs * 16 + cfg.batch_size - 1) // cfg.batch_size),
+                train_fused_update_off=off, train_fused_update_on=on,
+                ranges_overlap=not (on["max_ms"] < off["min_ms"]),
+                on_median_below_off_median=on["median_ms"] < off["median_ms"],
+                ratio_off_over_on=off["median_ms"] / on["median_ms"])
+
+
+def part_update_parity(args):
+    """tests/test_fused_update_gpu.py's yardstick on its synthetic batch at the minibatch's size (every adv_mode, value
+    clipping on and off, through sel) and on three Adam steps at the arena's size."""
+    import torch
+    import test_fused_update_gpu as U
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU")
+    n = args.parity_samples
+
+    def pack(rows):
+        return {name: dict(kernel_abs_dev_vs_fp64=dev, torch_fp32_gpu_abs_dev_vs_fp64=e, bound=bound,
+                           ratio=dev / bound if bound else 0.0) for name, dev, e, bound in rows}
+
+    loss = {}
+    for adv_mode in (0, 1, 2):
+        for vclip in (True, False):
+            rows, _, _ = U._loss_compare(n, adv_mode, vclip, True)
+            loss["adv_mode %d value_clip %d" % (adv_mode, vclip)] = pack(rows)
+    words = U._adam_sizes()[-1]
+    adam = {case: pack(U._adam_compare(words, case)[0]) for case in ("clip", "noclip", "off")}
+    worst = lambda d: max(v["ratio"] for c in d.values() for v in c.values())  # noqa: E731
+    return dict(samples=n, arena_words=words, ppo_loss=loss, adam_step=adam, worst_ratio_ppo_loss=worst(loss),
+                worst_ratio_adam_step=worst(adam))
+
+
 PARTS = {"step": (part_step, 420), "train": (part_train, 540), "parity": (part_parity, 540),
-         "mission_step": (part_mission_step, 420), "mission_parity": (part_mission_parity, 300)}
+         "mission_step": (part_mission_step, 420), "mission_parity": (part_mission_parity, 300),
+         "update_step": (part_update_step, 300), "update_train": (part_update_train, 420),
+         "update_parity": (part_update_parity, 300)}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default: profiles/r10_policy_train (r12_mission_gru with --fused-mission)")
     ap.add_argument("--fused-mission", action="store_true", help="measure the fused mission encoder instead")
+    ap.add_argument("--fused-update", action="store_true", help="measure the fused PPO update instead")
     ap.add_argument("--sha", default=None, help="build id to record (default: git rev-parse HEAD)")
     ap.add_argument("--envs", type=int, default=65536)
     ap.add_argument("--repeats", type=int, default=20)
@@ -304,9 +470,11 @@ def main():
     if args.repeats < 20:
         ap.error("--repeats must be >= 20")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "r12_mission_gru" if args.fused_mission else "r10_policy_train")
+        args.out = os.path.join(ROOT, "profiles", "r13_ppo_update" if args.fused_update else
+                                "r12_mission_gru" if args.fused_mission else "r10_policy_train")
     if args.parts is None:
-        args.parts = "mission_parity,mission_step" if args.fused_mission else "parity,step,train"
+        args.parts = ("update_parity,update_step,update_train" if args.fused_update else
+                      "mission_parity,mission_step" if args.fused_mission else "parity,step,train")
     sha = args.sha
     if sha is None:
         try:
@@ -336,6 +504,15 @@ def main():
     if "mission_step" in res:
         with open(os.path.join(args.out, "train.json"), "w") as f:
             json.dump(dict(meta, **res["mission_step"]), f, indent=1, sort_keys=True)
+            f.write("\n")
+    if "update_parity" in res:
+        with open(os.path.join(args.out, "parity.json"), "w") as f:
+            json.dump(dict(meta, **res["update_parity"]), f, indent=1, sort_keys=True)
+            f.write("\n")
+    if "update_step" in res or "update_train" in res:
+        with open(os.path.join(args.out, "train.json"), "w") as f:
+            json.dump(dict(meta, step=res.get("update_step"), train=res.get("update_train")), f, indent=1,
+                      sort_keys=True)
             f.write("\n")
     if "parity" in res:
         with open(os.path.join(args.out, "parity.json"), "w") as f:
