@@ -23,6 +23,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mgx.h"
@@ -2603,6 +2604,41 @@ __global__ __launch_bounds__(256) void mgx_observe_kernel(KParams p, uint8_t *__
     mids[e] = st.mission_id;
 }
 
+constexpr int MAX_NSTACK = 8;   // the kernels specialised on n_stack exist for 1 .. MAX_NSTACK (for_n_stack)
+
+// The frame-stack walk-back: the flat index (row * N + env) of the row `steps` rows behind row idx, or -1 when an
+// episode start lies in between, i.e. one of the rows 0 .. steps - 1 behind idx has starts[row] = 1 (that row is an
+// episode's first observation).  A linear buffer (R = 0), or a ring of R rows (mgx_gather_ring: the rows wrap, so a
+// rollout's history rows need no copy).
+__device__ __forceinline__ int64_t stack_back(int64_t idx, int64_t N, int64_t R, const uint8_t *__restrict__ starts,
+                                              int steps) {
+    const int64_t row0 = idx / N, env = idx - row0 * N;
+    const auto back_idx = [&](int j) -> int64_t {
+        int64_t r = row0 - j;
+        if (R > 0 && r < 0) r += ((-r + R - 1) / R) * R;
+        return r * N + env;
+    };
+    for (int j = 0; j < steps; j++)
+        if (starts[back_idx(j)]) return -1;
+    return back_idx(steps);
+}
+
+// The compact row that fills the slot `back` steps behind the newest frame of sample idx, and its mission id; nullptr
+// and -1 for an empty slot (VecFrameStack's reset zeroing).  With `newest` (terminal rows [N][FROW]) the newest frame
+// is env's terminal row and the older frames start at row idx itself: the same walk with one step fewer, because the
+// terminal row continues row idx's episode.
+__device__ __forceinline__ const uint8_t *stack_slot(const uint8_t *__restrict__ rows, const uint8_t *__restrict__ mids,
+                                                     const uint8_t *__restrict__ starts, int64_t N, int64_t R,
+                                                     const uint8_t *__restrict__ newest, int64_t idx, int back, int &mid) {
+    if (newest && back == 0) {
+        mid = mids[idx];
+        return newest + idx % N * FROW;
+    }
+    const int64_t r = stack_back(idx, N, R, starts, newest ? back - 1 : back);
+    mid = r >= 0 ? mids[r] : -1;
+    return r >= 0 ? rows + r * FROW : nullptr;
+}
+
 // mgx_gather: SB3 stacked observations (VecTransposeImage + VecFrameStack(n_stack)) rebuilt
 // from compact rows.  Sample b's newest frame is row index[b] (flat row*N + env) -- or, with
 // `newest` (terminal rows [N][148]), env's terminal row, the older frames then starting at
@@ -2616,7 +2652,6 @@ __global__ __launch_bounds__(256) void mgx_observe_kernel(KParams p, uint8_t *__
 // coalesced along a row; rows are 148 B = 37 dwords), phase B writes the tile's outputs,
 // which are contiguous in memory, with consecutive threads on consecutive dwords.
 constexpr int GATHER_TILE = 16;
-constexpr int GATHER_MAXK = 8;
 template <int K, bool F32>   // n_stack and output type are compile-time: every index split is a constant division
 __global__ __launch_bounds__(256) void mgx_gather_kernel(const uint8_t *__restrict__ rows, const uint8_t *__restrict__ mids,
                                                          const uint8_t *__restrict__ starts, int64_t N, int64_t R,
@@ -2634,35 +2669,8 @@ __global__ __launch_bounds__(256) void mgx_gather_kernel(const uint8_t *__restri
     // phase A1: per (sample, slot): source row and validity
     __shared__ const uint8_t *s_src[GATHER_TILE * K];
     if (tid < npair) {
-        const int bi = tid / K, k = tid - bi * K;                        // k = slot (K-1 = newest)
-        const int64_t idx = index[b0 + bi];
-        const int64_t row0 = idx / N, env = idx - row0 * N;
-        // flat index of the row j steps before the newest: linear buffer (R = 0), or a ring of R rows
-        // (mgx_gather_ring: the rows wrap, so a rollout's history rows need no copy)
-        const auto back_idx = [&](int j) -> int64_t {
-            int64_t r = row0 - j;
-            if (R > 0 && r < 0) r += ((-r + R - 1) / R) * R;
-            return r * N + env;
-        };
-        const int back = K - 1 - k;                                      // steps back from the newest
-        const uint8_t *src = nullptr;
-        int mid = -1;
-        if (newest) {
-            // newest = terminal row; older slot j back = row idx - (j-1)*N, valid while no start
-            // among rows idx .. idx - (j-2)*N (the terminal row itself continues the episode)
-            if (back == 0) { src = newest + env * FROW; mid = mids[idx]; }
-            else {
-                bool ok = true;
-                for (int j = 0; j < back - 1 && ok; j++) ok = !starts[back_idx(j)];
-                if (ok) { const int64_t r = back_idx(back - 1); src = rows + r * FROW; mid = mids[r]; }
-            }
-        } else {
-            bool ok = true;
-            for (int j = 0; j < back && ok; j++) ok = !starts[back_idx(j)];
-            if (ok) { const int64_t r = back_idx(back); src = rows + r * FROW; mid = mids[r]; }
-        }
-        s_src[tid] = src;
-        s_mid[tid] = mid;
+        const int bi = tid / K, k = tid - bi * K;                        // k = slot (K-1 = newest, 0 steps back)
+        s_src[tid] = stack_slot(rows, mids, starts, N, R, newest, index[b0 + bi], K - 1 - k, s_mid[tid]);
     }
     __syncthreads();
     // phase A2: stage the rows (37 dwords each)
@@ -2744,6 +2752,18 @@ mgx_status fail(mgx_status s, const std::string &msg) {
         hipError_t _e = (expr);                                                                        \
         if (_e != hipSuccess) return fail(MGX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
     } while (0)
+
+// Calls f(std::integral_constant<int, n_stack>) for n_stack in 1 .. MAX_NSTACK: the one place that instantiates the
+// kernels specialised on the stack depth.  false, and f not called, for any other n_stack.
+template <int KK = 1, class F>
+static bool for_n_stack(int n_stack, F &&f) {
+    if constexpr (KK <= MAX_NSTACK) {
+        if (n_stack != KK) return for_n_stack<KK + 1>(n_stack, f);
+        f(std::integral_constant<int, KK>{});
+        return true;
+    }
+    return false;
+}
 
 // CPython random.seed(n) -> MT19937 init_by_array(32-bit chunks of n)
 struct HostMT {
@@ -3219,23 +3239,18 @@ mgx_status mgx_create(const mgx_config *cfg, int device, mgx_handle **out) {
     MGX_SET_LDS(mgx_scene_kernel, h->lds_refill);
 #undef MGX_SET_LDS
 #undef MGX_SET_LDS1
-    switch (cfg->n_stack) {   // mgx_policy_act: this handle's n_stack only
-#define MGX_POL_LDS(KK) \
-    case KK: HIP_TRY(hipFuncSetAttribute((const void *)mgx_policy_kernel<KK>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                         (int)pol_lds_bytes(KK))); break;
-        MGX_POL_LDS(1) MGX_POL_LDS(2) MGX_POL_LDS(3) MGX_POL_LDS(4) MGX_POL_LDS(5) MGX_POL_LDS(6) MGX_POL_LDS(7) MGX_POL_LDS(8)
-#undef MGX_POL_LDS
-        default: break;
-    }
-    h->pol_grad_lds = false;
-    switch (cfg->n_stack) {   // mgx_policy_backward: a refusal here fails that call, not the handle
-#define MGX_PG_LDS(KK) \
-    case KK: h->pol_grad_lds = hipFuncSetAttribute((const void *)mgx_policy_grad_kernel<KK>, \
-                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)pg_lds_bytes()) == hipSuccess; break;
-        MGX_PG_LDS(1) MGX_PG_LDS(2) MGX_PG_LDS(3) MGX_PG_LDS(4) MGX_PG_LDS(5) MGX_PG_LDS(6) MGX_PG_LDS(7) MGX_PG_LDS(8)
-#undef MGX_PG_LDS
-        default: break;
-    }
+    // the dynamic LDS of this handle's n_stack only.  mgx_policy_backward: a refusal fails that call, not the handle
+    hipError_t pol_lds = hipSuccess, pol_grad_lds = hipErrorInvalidValue;
+    for_n_stack(cfg->n_stack, [&](auto kk) {
+        constexpr int KK = decltype(kk)::value;
+        pol_lds = hipFuncSetAttribute((const void *)mgx_policy_kernel<KK>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)pol_lds_bytes(KK));
+        if (pol_lds == hipSuccess)
+            pol_grad_lds = hipFuncSetAttribute((const void *)mgx_policy_grad_kernel<KK>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)pg_lds_bytes());
+    });
+    HIP_TRY(pol_lds);
+    h->pol_grad_lds = pol_grad_lds == hipSuccess;
     if (!h->pol_grad_lds) (void)hipGetLastError();
     {
         hipError_t e = hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking);
@@ -3716,6 +3731,19 @@ mgx_status mgx_observe_compact(mgx_handle *h, uint8_t *row_dev, uint8_t *mission
     return MGX_OK;
 }
 
+// The sample addressing shared by mgx_gather_ring, mgx_policy_act and mgx_policy_backward, checked and filled into *s.
+// 0: fine; 1: a null pointer or a count out of range; 2: a ring that cannot hold n_stack rows.  The callers word
+// their own messages.
+static int sample_addr(const mgx_handle *h, const uint8_t *rows_dev, const uint8_t *mission_ids_dev,
+                       const uint8_t *starts_dev, int64_t n_envs, int64_t ring_rows, const int64_t *index_dev,
+                       int64_t n_samples, SampleAddr *s) {
+    if (!h || !rows_dev || !mission_ids_dev || !starts_dev || !index_dev || n_envs <= 0 || n_samples < 0 || ring_rows < 0)
+        return 1;
+    if (ring_rows > 0 && ring_rows < h->kp.n_stack) return 2;
+    *s = SampleAddr{rows_dev, mission_ids_dev, starts_dev, n_envs, ring_rows, index_dev, n_samples};
+    return 0;
+}
+
 mgx_status mgx_gather(const mgx_handle *h, const uint8_t *rows_dev, const uint8_t *mission_ids_dev,
                       const uint8_t *starts_dev, int64_t n_envs, const int64_t *index_dev, int64_t n_samples,
                       const uint8_t *terminal_rows_dev, void *image_dev, int image_f32, void *direction_dev,
@@ -3728,32 +3756,21 @@ mgx_status mgx_gather_ring(const mgx_handle *h, const uint8_t *rows_dev, const u
                            const uint8_t *starts_dev, int64_t n_envs, int64_t ring_rows, const int64_t *index_dev,
                            int64_t n_samples, const uint8_t *terminal_rows_dev, void *image_dev, int image_f32,
                            void *direction_dev, int direction_f32, uint8_t *mission_dev, void *stream) {
-    if (!h || !rows_dev || !mission_ids_dev || !starts_dev || !index_dev || !image_dev || !direction_dev ||
-        !mission_dev || n_envs <= 0 || n_samples < 0 || ring_rows < 0)
-        return fail(MGX_ERR_INVALID, "mgx_gather: bad argument");
-    if (ring_rows > 0 && ring_rows < h->kp.n_stack)
-        return fail(MGX_ERR_INVALID, "mgx_gather_ring: the ring must hold n_stack rows");
-    const int K = h->kp.n_stack;
-    if (K > GATHER_MAXK) return fail(MGX_ERR_INVALID, "mgx_gather: n_stack > 8");
+    SampleAddr s;
+    const int bad = sample_addr(h, rows_dev, mission_ids_dev, starts_dev, n_envs, ring_rows, index_dev, n_samples, &s);
+    if (bad == 1 || !image_dev || !direction_dev || !mission_dev) return fail(MGX_ERR_INVALID, "mgx_gather: bad argument");
+    if (bad == 2) return fail(MGX_ERR_INVALID, "mgx_gather_ring: the ring must hold n_stack rows");
+    if (h->kp.n_stack > MAX_NSTACK) return fail(MGX_ERR_INVALID, "mgx_gather: n_stack > 8");
     if (n_samples == 0) return MGX_OK;
     if (!image_f32 != !direction_f32) return fail(MGX_ERR_INVALID, "mgx_gather: image and direction share one dtype");
     const int64_t nblk = (n_samples + GATHER_TILE - 1) / GATHER_TILE;
-#define MGX_GATHER(KK)                                                                                           \
-    case KK:                                                                                                     \
-        if (image_f32)                                                                                           \
-            hipLaunchKernelGGL((mgx_gather_kernel<KK, true>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, \
-                               rows_dev, mission_ids_dev, starts_dev, n_envs, ring_rows, index_dev, n_samples, terminal_rows_dev, \
-                               h->kp.mtok, image_dev, direction_dev, mission_dev);                              \
-        else                                                                                                     \
-            hipLaunchKernelGGL((mgx_gather_kernel<KK, false>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, \
-                               rows_dev, mission_ids_dev, starts_dev, n_envs, ring_rows, index_dev, n_samples, terminal_rows_dev, \
-                               h->kp.mtok, image_dev, direction_dev, mission_dev);                              \
-        break;
-    switch (K) {
-        MGX_GATHER(1) MGX_GATHER(2) MGX_GATHER(3) MGX_GATHER(4) MGX_GATHER(5) MGX_GATHER(6) MGX_GATHER(7) MGX_GATHER(8)
-        default: return fail(MGX_ERR_INVALID, "mgx_gather: n_stack out of range");
-    }
-#undef MGX_GATHER
+    const bool launched = for_n_stack(h->kp.n_stack, [&](auto kk) {
+        constexpr int KK = decltype(kk)::value;
+        const auto kernel = image_f32 ? mgx_gather_kernel<KK, true> : mgx_gather_kernel<KK, false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, s.rows, s.mids, s.starts, s.N,
+                           s.R, s.index, s.B, terminal_rows_dev, h->kp.mtok, image_dev, direction_dev, mission_dev);
+    });
+    if (!launched) return fail(MGX_ERR_INVALID, "mgx_gather: n_stack out of range");
     HIP_TRY(hipGetLastError());
     return MGX_OK;
 }
@@ -3808,7 +3825,7 @@ mgx_status mgx_random_actions(int32_t *out_dev, int64_t count, int n_actions, ui
 }
 
 int64_t mgx_policy_blob_words(int n_stack) {
-    return n_stack >= 1 && n_stack <= 8 ? (int64_t)pol_blob(n_stack).words : -1;
+    return n_stack >= 1 && n_stack <= MAX_NSTACK ? (int64_t)pol_blob(n_stack).words : -1;
 }
 
 mgx_status mgx_policy_act(const mgx_handle *h, const uint8_t *rows_dev, const uint8_t *mission_ids_dev,
@@ -3822,28 +3839,22 @@ mgx_status mgx_policy_act(const mgx_handle *h, const uint8_t *rows_dev, const ui
     if (pol->mode == 2 && !pol->counter_dev) return fail(MGX_ERR_INVALID, "mgx_policy_act: mode 2 needs counter_dev");
     if (pol->mode != 0 && (!out->actions_dev || !out->log_probs_dev))
         return fail(MGX_ERR_INVALID, "mgx_policy_act: modes 1 and 2 need actions_dev and log_probs_dev");
-    if (!h || !rows_dev || !mission_ids_dev || !starts_dev || !index_dev || n_envs <= 0 || ring_rows < 0)
-        return fail(MGX_ERR_INVALID, "mgx_policy_act: bad sample addressing");
-    const int K = h->kp.n_stack;
-    if (ring_rows > 0 && ring_rows < K) return fail(MGX_ERR_INVALID, "mgx_policy_act: the ring must hold n_stack rows");
     PolArgs a;
-    a.rows = rows_dev; a.mids = mission_ids_dev; a.starts = starts_dev;
-    a.N = n_envs; a.R = ring_rows; a.index = index_dev; a.B = n_samples; a.newest = terminal_rows_dev;
+    const int bad = sample_addr(h, rows_dev, mission_ids_dev, starts_dev, n_envs, ring_rows, index_dev, n_samples, &a.s);
+    if (bad == 1) return fail(MGX_ERR_INVALID, "mgx_policy_act: bad sample addressing");
+    if (bad == 2) return fail(MGX_ERR_INVALID, "mgx_policy_act: the ring must hold n_stack rows");
+    a.newest = terminal_rows_dev;
     a.blob = pol->blob_dev; a.mfeat = pol->mission_feat_dev; a.mode = pol->mode; a.seed = pol->seed;
     a.ctr = (unsigned long long *)pol->counter_dev;
     a.actions = (long long *)out->actions_dev; a.values = out->values_dev; a.log_probs = out->log_probs_dev;
     a.logits = out->logits_dev;
     const int64_t nblk = (n_samples + POL_TILE - 1) / POL_TILE;
-#define MGX_POL(KK)                                                                                              \
-    case KK:                                                                                                     \
-        hipLaunchKernelGGL(mgx_policy_kernel<KK>, dim3((unsigned)nblk), dim3(POL_THREADS), pol_lds_bytes(KK),            \
-                           (hipStream_t)stream, a);                                                              \
-        break;
-    switch (K) {
-        MGX_POL(1) MGX_POL(2) MGX_POL(3) MGX_POL(4) MGX_POL(5) MGX_POL(6) MGX_POL(7) MGX_POL(8)
-        default: return fail(MGX_ERR_INVALID, "mgx_policy_act: n_stack out of range");
-    }
-#undef MGX_POL
+    const bool launched = for_n_stack(h->kp.n_stack, [&](auto kk) {
+        constexpr int KK = decltype(kk)::value;
+        hipLaunchKernelGGL(mgx_policy_kernel<KK>, dim3((unsigned)nblk), dim3(POL_THREADS), pol_lds_bytes(KK),
+                           (hipStream_t)stream, a);
+    });
+    if (!launched) return fail(MGX_ERR_INVALID, "mgx_policy_act: n_stack out of range");
     HIP_TRY(hipGetLastError());
     return MGX_OK;
 }
@@ -3854,7 +3865,7 @@ static int pol_grad_groups(int64_t n_samples, int max_groups) {
 }
 
 int64_t mgx_policy_grad_scratch_words(int n_stack, int64_t n_samples, int max_groups) {
-    if (n_stack < 1 || n_stack > 8 || n_samples <= 0 || max_groups < 0) return -1;
+    if (n_stack < 1 || n_stack > MAX_NSTACK || n_samples <= 0 || max_groups < 0) return -1;
     return (int64_t)pol_grad_groups(n_samples, max_groups) * pol_blob(n_stack).words;
 }
 
@@ -3869,33 +3880,24 @@ mgx_status mgx_policy_backward(const mgx_handle *h, const uint8_t *rows_dev, con
     if (n_samples <= 0) return fail(MGX_ERR_INVALID, "mgx_policy_backward: n_samples must be > 0");
     if (g->max_groups < 0) return fail(MGX_ERR_INVALID, "mgx_policy_backward: max_groups must be >= 0");
     if (g->scratch_words <= 0) return fail(MGX_ERR_INVALID, "mgx_policy_backward: scratch_words must be > 0");
-    if (!h || !rows_dev || !mission_ids_dev || !starts_dev || !index_dev || n_envs <= 0 || ring_rows < 0)
-        return fail(MGX_ERR_INVALID, "mgx_policy_backward: bad sample addressing");
+    PolGradArgs a;
+    const int bad = sample_addr(h, rows_dev, mission_ids_dev, starts_dev, n_envs, ring_rows, index_dev, n_samples, &a.s);
+    if (bad == 1) return fail(MGX_ERR_INVALID, "mgx_policy_backward: bad sample addressing");
     const int K = h->kp.n_stack;
-    if (K < 1 || K > 8) return fail(MGX_ERR_INVALID, "mgx_policy_backward: n_stack out of range");
-    if (ring_rows > 0 && ring_rows < K)
-        return fail(MGX_ERR_INVALID, "mgx_policy_backward: the ring must hold n_stack rows");
+    if (K < 1 || K > MAX_NSTACK) return fail(MGX_ERR_INVALID, "mgx_policy_backward: n_stack out of range");
+    if (bad == 2) return fail(MGX_ERR_INVALID, "mgx_policy_backward: the ring must hold n_stack rows");
     if (g->scratch_words < mgx_policy_grad_scratch_words(K, n_samples, g->max_groups))
         return fail(MGX_ERR_INVALID, "mgx_policy_backward: scratch_words below mgx_policy_grad_scratch_words");
     if (!h->pol_grad_lds) return fail(MGX_ERR_HIP, "mgx_policy_backward: the device refused the kernel's LDS");
-    PolGradArgs a;
-    a.rows = rows_dev; a.mids = mission_ids_dev; a.starts = starts_dev;
-    a.N = n_envs; a.R = ring_rows; a.index = index_dev; a.B = n_samples;
     a.blob = g->blob_dev; a.mfeat = g->mission_feat_dev; a.g_logits = g->g_logits_dev; a.g_values = g->g_values_dev;
     a.gmf = g->grad_mission_feat_dev; a.scratch = g->scratch_dev;
     a.groups = pol_grad_groups(n_samples, g->max_groups);
     const int words = pol_blob(K).words;
     HIP_TRY(hipMemsetAsync(g->grad_mission_feat_dev, 0, (size_t)256 * K * 128 * sizeof(float), (hipStream_t)stream));
-#define MGX_PG(KK)                                                                                               \
-    case KK:                                                                                                     \
-        hipLaunchKernelGGL(mgx_policy_grad_kernel<KK>, dim3((unsigned)a.groups), dim3(POL_THREADS), pg_lds_bytes(), \
-                           (hipStream_t)stream, a);                                                              \
-        break;
-    switch (K) {
-        MGX_PG(1) MGX_PG(2) MGX_PG(3) MGX_PG(4) MGX_PG(5) MGX_PG(6) MGX_PG(7) MGX_PG(8)
-        default: break;
-    }
-#undef MGX_PG
+    for_n_stack(K, [&](auto kk) {
+        hipLaunchKernelGGL(mgx_policy_grad_kernel<decltype(kk)::value>, dim3((unsigned)a.groups), dim3(POL_THREADS),
+                           pg_lds_bytes(), (hipStream_t)stream, a);
+    });
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(mgx_policy_fold_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const float *)g->scratch_dev, a.groups, words, g->grad_blob_dev);

@@ -1,6 +1,6 @@
 // mgx_policy.h -- mgx_policy_act: the reference actor-critic's forward pass (policy.py DEFAULT_ARCH, net_arch 64/64
 // Tanh, 7 actions) straight from compact rows: actions, values, log-probs and logits of n samples in ONE launch, the
-// stacked observation never materialised.  Included by mgx_engine.hip (after splitmix64 and FROW).
+// stacked observation never materialised.  Included by mgx_engine.hip (after splitmix64, FROW and stack_slot).
 //
 // Mapping (DESIGN.md "Fused actor-critic kernel"): one workgroup of 8 waves per tile of 64 samples.  LANE = SAMPLE in
 // every stage; the 8 waves split each layer's OUTPUT channels.  A lane keeps 8..16 fp32 accumulators in registers;
@@ -10,17 +10,23 @@
 // feature i of its own sample, consecutive lanes hit consecutive banks.  All 64 lanes are busy in every stage of a
 // full tile; a tail tile computes zeros in its spare lanes and writes nothing for them.
 //
-//   A   per (sample, slot): source row / validity (mgx_gather's walk-back, ring wrap and terminal rows included)
-//   A2  rows -> LDS as dwords [slot][37][65] (coalesced along a row; empty slot = zeros)
-//   B   conv1 2x2 + ReLU + MaxPool 2: rows (X) -> P[144]; each lane keeps its K direction bytes in a register
-//   C   conv2 2x2 + ReLU: P -> C2[128] in X (the rows are dead)
-//   D   conv3 2x2 + ReLU: C2 -> F[16..80) in P (dead after C); direction Linear (one weight column per valid
-//       slot) -> F[0..16)
-//   E   policy_net L0 | value_net_body L0 (208 -> 64 each, Tanh): F + mission_feat[mid][v-1][128] (global) -> H1[128] in X
-//   F   policy_net L1 | value_net_body L1 (64 -> 64 each, Tanh): H1 -> H2[128] in P
-//   G   action_net (7) and value_net (1), arg-max / inverse-cdf sample, log-prob: wave 0
-// Two LDS regions in all, X = max(37 K, 128) rows and P = 144 rows of 65 dwords: 79 KB at n_stack 4, two workgroups
-// per CU.
+// Stages A to F are the pol_* function templates below, each taking its source and destination LDS regions: they are
+// the network's one forward pass, run by mgx_policy_kernel here and by pass (a) of mgx_policy_grad_kernel
+// (mgx_policy_grad.h), so the gradient is that of the logits mgx_policy_act returns.
+//
+//   A   pol_stage_src   per (sample, slot): source row / validity (stack_slot: mgx_gather's walk-back, ring wrap and
+//                       terminal rows included)
+//   A2  pol_stage_rows  rows -> LDS as dwords [slot][37][65] (coalesced along a row; empty slot = zeros)
+//   B   pol_conv1       conv1 2x2 + ReLU + MaxPool 2: rows -> P[144]; before it each lane packs its K direction bytes
+//                       into a register (pol_dsel)
+//   C   pol_conv2       conv2 2x2 + ReLU: P -> C2[128]
+//   D   pol_conv3_dir   conv3 2x2 + ReLU: C2 -> F[16..80); direction Linear (one weight column per valid slot) -> F[0..16)
+//   E   pol_l0          policy_net L0 | value_net_body L0 (208 -> 64 each, Tanh): F + mission_feat[mid][v-1][128]
+//                       (global) -> H1[128]
+//   F   pol_l1          policy_net L1 | value_net_body L1 (64 -> 64 each, Tanh): H1 -> H2[128]
+//   G   action_net (7) and value_net (1), arg-max / inverse-cdf sample, log-prob: wave 0 of mgx_policy_kernel
+// mgx_policy_kernel has two LDS regions in all, X = max(37 K, 128) rows (the rows, then C2, then H1) and P = 144 rows
+// (the pooled maps, then F, then H2) of 65 dwords: 79 KB at n_stack 4, two workgroups per CU.
 // fp32 throughout, every multiply-add an explicit fmaf (the library is built with -ffp-contract=off).
 #ifndef MGX_POLICY_H_
 #define MGX_POLICY_H_
@@ -32,6 +38,7 @@ constexpr int POL_LS = 65;                 // LDS row stride in dwords (64 sampl
 constexpr int POL_RW = FROW / 4;           // 37 dwords per compact row
 constexpr int POL_FEAT = 208;              // direction 16 | image 64 | mission 128
 constexpr int POL_NA = 7;
+constexpr int POL_NF = 64 / POL_NW;        // outputs per wave of a 64-wide layer
 
 // Offsets (fp32 words) of the packed weight blob, in include/mgx.h's order.
 struct PolBlob {
@@ -60,11 +67,18 @@ static_assert(pol_blob(4).words == 46984, "blob layout");
 __host__ __device__ constexpr int pol_x_rows(int K) { return K * POL_RW > 128 ? K * POL_RW : 128; }
 __host__ __device__ constexpr size_t pol_lds_bytes(int K) { return (size_t)(pol_x_rows(K) + 144) * POL_LS * 4; }
 
-struct PolArgs {
+// Which samples a launch works on: sample b's newest frame is row index[b] (flat row * N + env) of a compact buffer
+// of N envs, linear (R = 0) or a ring of R rows.  The leading arguments of mgx_gather_ring, mgx_policy_act and
+// mgx_policy_backward (sample_addr in mgx_engine.hip checks and fills it).
+struct SampleAddr {
     const uint8_t *rows, *mids, *starts;
     int64_t N, R;
     const int64_t *index;
     int64_t B;
+};
+
+struct PolArgs {
+    SampleAddr s;
     const uint8_t *newest;
     const float *blob, *mfeat;
     int mode;
@@ -104,6 +118,221 @@ __device__ __forceinline__ void pol_dot2(float (&a)[NO], float (&b)[NO], const f
         }
     }
 }
+// pol_dot's load4 for an input in LDS: features i0 .. i0 + 3 of the lane's sample (xin = the region + lane)
+__device__ __forceinline__ auto pol_lds4(const float *xin) {
+    return [xin](int i0, float (&x)[4]) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) x[j] = xin[(i0 + j) * POL_LS];
+    };
+}
+// the four outputs of a 2x2 convolution over a 3x3 input, one input channel: acc[oy][ox] += in[oy + dy][ox + dx] *
+// wq[dy][dx], the taps (dy, dx) in row order
+__device__ __forceinline__ void pol_conv2x2(const float (&in)[9], const float *__restrict__ wq, float (&acc)[4]) {
+#pragma unroll
+    for (int dy = 0; dy < 2; dy++)
+#pragma unroll
+        for (int dx = 0; dx < 2; dx++) {
+            const float wt = wq[dy * 2 + dx];
+#pragma unroll
+            for (int oy = 0; oy < 2; oy++)
+#pragma unroll
+                for (int ox = 0; ox < 2; ox++)
+                    acc[oy * 2 + ox] = __builtin_fmaf(in[(oy + dy) * 3 + ox + dx], wt, acc[oy * 2 + ox]);
+        }
+}
+
+// ---- The forward pass, stage by stage.  Common arguments: tid = thread of the workgroup, lane = tid & 63 = the
+// sample, wv = the wave (wave-uniform, so that weight addresses stay scalar), W = the weight blob; activations are
+// [feature][POL_LS] floats in LDS.  The caller puts a barrier between two stages.
+
+// ---- A: source row (nullptr: empty slot) and mission id (-1) of every (sample, slot) of the tile of nb samples at b0;
+// slot K-1 is the newest (mgx_gather_kernel's rules)
+template <int K>
+__device__ __forceinline__ void pol_stage_src(const SampleAddr &s, const uint8_t *newest, int64_t b0, int nb, int tid,
+                                              const uint8_t **s_src, int *s_mid) {
+    for (int pr = tid; pr < POL_TILE * K; pr += POL_THREADS) {
+        const int bi = pr / K, k = pr - bi * K;
+        const uint8_t *src = nullptr;
+        int mid = -1;
+        if (bi < nb) src = stack_slot(s.rows, s.mids, s.starts, s.N, s.R, newest, s.index[b0 + bi], K - 1 - k, mid);
+        s_src[pr] = src;
+        s_mid[pr] = mid;
+    }
+}
+// ---- A2: stage the rows: X[(k * 37 + w) * 65 + sample] = dword w of slot k
+template <int K>
+__device__ __forceinline__ void pol_stage_rows(const uint8_t *const *s_src, int tid, float *X) {
+    uint32_t *Xu = reinterpret_cast<uint32_t *>(X);
+    for (int i = tid; i < POL_TILE * K * POL_RW; i += POL_THREADS) {
+        const int pr = i / POL_RW, w = i - pr * POL_RW;
+        const int bi = pr / K, k = pr - bi * K;
+        const uint8_t *src = s_src[pr];
+        Xu[(k * POL_RW + w) * POL_LS + bi] = src ? reinterpret_cast<const uint32_t *>(src)[w] : 0u;
+    }
+}
+// valid slots are contiguous from the newest and share its mission id: v = their count.  Returns the lane's row of the
+// mission-feature table [256][K][128], mid * K + v - 1 (row 0 for a spare lane, whose slots are all empty)
+template <int K>
+__device__ __forceinline__ int pol_feat_row(const int *s_mid, int lane, int nb, int &v) {
+    v = 0;
+#pragma unroll
+    for (int k = 0; k < K; k++) v += s_mid[lane * K + k] >= 0;
+    const int my_mid = lane < nb ? s_mid[lane * K + K - 1] : 0;
+    return my_mid * K + (v > 0 ? v - 1 : 0);
+}
+// direction (row byte 0) of slot k at bits 2k; xb = the staged rows + lane * 4
+template <int K>
+__device__ __forceinline__ uint32_t pol_dsel(const uint8_t *xb) {
+    uint32_t dsel = 0;
+#pragma unroll
+    for (int k = 0; k < K; k++) dsel |= (uint32_t)(xb[(k * POL_RW) * POL_LS * 4] & 3) << (2 * k);
+    return dsel;
+}
+// conv1's 3x3 input patch under pooled cell (py, px) of input channel c (slot c / 3, colour c % 3); pixel = u8 / 255
+__device__ __forceinline__ void pol_conv1_patch(const uint8_t *xb, int c, int py, int px, float (&pix)[9]) {
+    const int k = c / 3, ch = c - k * 3;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const int bp = 1 + ch * 49 + (2 * py + i) * 7 + 2 * px + j;      // byte of the row
+            pix[i * 3 + j] = (float)xb[((k * POL_RW + (bp >> 2)) * POL_LS) * 4 + (bp & 3)] * (1.0f / 255.0f);
+        }
+}
+// conv1's four outputs under pooled cell `cell` for output channels oc0 .. oc0 + 3, from a 3x3 patch per input channel
+// (16 accumulators, 64 fmaf per 9 pixels)
+template <int K>
+__device__ __forceinline__ void pol_conv1_cell(const float *__restrict__ W, const uint8_t *xb, int oc0, int cell,
+                                               float (&acc)[4][4]) {
+    constexpr PolBlob L = pol_blob(K);
+    const int py = cell / 3, px = cell - py * 3;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const float bq = W[L.c1_b + oc0 + q];
+#pragma unroll
+        for (int p = 0; p < 4; p++) acc[q][p] = bq;
+    }
+#pragma nounroll                       // (at n_stack 2 the 6 trips were unrolled: 284 scalar registers spilled)
+    for (int c = 0; c < 3 * K; c++) {
+        float pix[9];
+        pol_conv1_patch(xb, c, py, px, pix);
+#pragma unroll
+        for (int q = 0; q < 4; q++) pol_conv2x2(pix, W + L.c1_w + ((oc0 + q) * 3 * K + c) * 4, acc[q]);
+    }
+}
+// a wave's share of conv1's (output channel, pooled cell) pairs: 4 output channels x 5 or 4 of the 9 cells
+__device__ __forceinline__ void pol_conv1_share(int wv, int &oc0, int &cell0, int &cell1) {
+    oc0 = (wv & 3) * 4;
+    cell0 = (wv >> 2) ? 5 : 0;
+    cell1 = (wv >> 2) ? 9 : 5;
+}
+// ---- B: conv1 (3K -> 16, 2x2) + ReLU + MaxPool 2: the rows -> P[144]
+template <int K>
+__device__ __forceinline__ void pol_conv1(const float *__restrict__ W, int wv, int lane, const uint8_t *xb, float *P) {
+    int oc0, cell0, cell1;
+    pol_conv1_share(wv, oc0, cell0, cell1);
+    for (int cell = cell0; cell < cell1; cell++) {
+        float acc[4][4];
+        pol_conv1_cell<K>(W, xb, oc0, cell, acc);
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            P[((oc0 + q) * 9 + cell) * POL_LS + lane] =
+                fmaxf(fmaxf(fmaxf(acc[q][0], acc[q][1]), fmaxf(acc[q][2], acc[q][3])), 0.0f);
+    }
+}
+// ---- C: conv2 (16 -> 32, 2x2 on 3x3) + ReLU: P -> C2[128]; wave = 4 output channels x 4 positions (16 accumulators)
+template <int K>
+__device__ __forceinline__ void pol_conv2(const float *__restrict__ W, int wv, int lane, const float *P, float *C2) {
+    constexpr PolBlob L = pol_blob(K);
+    constexpr int LS = POL_LS;
+    constexpr int NQ = 32 / POL_NW;
+    const int oc0 = wv * NQ;
+    float acc[NQ][4];
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+        const float bq = W[L.c2_b + oc0 + q];
+#pragma unroll
+        for (int p = 0; p < 4; p++) acc[q][p] = bq;
+    }
+    for (int ic = 0; ic < 16; ic++) {
+        float in[9];
+#pragma unroll
+        for (int j = 0; j < 9; j++) in[j] = P[(ic * 9 + j) * LS + lane];
+#pragma unroll
+        for (int q = 0; q < NQ; q++) pol_conv2x2(in, W + L.c2_w + ((oc0 + q) * 16 + ic) * 4, acc[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; q++)
+#pragma unroll
+        for (int p = 0; p < 4; p++) C2[((oc0 + q) * 4 + p) * LS + lane] = fmaxf(acc[q][p], 0.0f);
+}
+// ---- D: conv3 (32 -> 64, 2x2 on 2x2 = a 128 -> 64 dot) + ReLU: C2 -> F[16 .. 80), wave = 8 output channels; direction
+// Linear(4K -> 16): bias + one weight column per valid slot (one-hot input) -> F[0 .. 16), wave = 2 outputs
+template <int K>
+__device__ __forceinline__ void pol_conv3_dir(const float *__restrict__ W, int wv, int lane, uint32_t dsel, int v,
+                                              const float *C2, float *F) {
+    constexpr PolBlob L = pol_blob(K);
+    constexpr int LS = POL_LS, NF = POL_NF;
+    const int o0 = wv * NF;
+    float acc[NF];
+#pragma unroll
+    for (int o = 0; o < NF; o++) acc[o] = W[L.c3_b + o0 + o];
+    pol_dot<NF>(acc, W + L.c3_w + o0 * 128, 128, 128, pol_lds4(C2 + lane));
+#pragma unroll
+    for (int o = 0; o < NF; o++) F[(16 + o0 + o) * LS + lane] = fmaxf(acc[o], 0.0f);
+#pragma unroll
+    for (int q = 0; q < 16 / POL_NW; q++) {
+        const int o = wv * (16 / POL_NW) + q;
+        float acc1 = W[L.dir_b + o];
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            const float wt = W[L.dir_w + o * 4 * K + 4 * k + ((dsel >> (2 * k)) & 3)];
+            acc1 = __builtin_fmaf(k >= K - v ? 1.0f : 0.0f, wt, acc1);
+        }
+        F[o * LS + lane] = acc1;
+    }
+}
+// ---- E: policy_net L0 | value_net_body L0: 208 -> 64 each, Tanh; wave = 8 + 8 outputs sharing every input.
+// Inputs 0..79 from F, 80..207 the (mission, v) feature row mf, read by each lane from the table (float4).
+// H1: [0..64) policy, [64..128) value
+template <int K>
+__device__ __forceinline__ void pol_l0(const float *__restrict__ W, int wv, int lane, const float *__restrict__ mf,
+                                       const float *F, float *H1) {
+    constexpr PolBlob L = pol_blob(K);
+    constexpr int LS = POL_LS, NF = POL_NF;
+    float hp[NF], hv[NF];
+    const int o0 = wv * NF;
+#pragma unroll
+    for (int o = 0; o < NF; o++) { hp[o] = W[L.p0_b + o0 + o]; hv[o] = W[L.v0_b + o0 + o]; }
+    pol_dot2<NF>(hp, hv, W + L.p0_w + o0 * POL_FEAT, W + L.v0_w + o0 * POL_FEAT, POL_FEAT, 80, pol_lds4(F + lane));
+    pol_dot2<NF>(hp, hv, W + L.p0_w + o0 * POL_FEAT + 80, W + L.v0_w + o0 * POL_FEAT + 80, POL_FEAT, 128,
+                 [&](int i0, float (&x)[4]) {
+                     const float4 m = *reinterpret_cast<const float4 *>(mf + i0);
+                     x[0] = m.x; x[1] = m.y; x[2] = m.z; x[3] = m.w;
+                 });
+#pragma unroll
+    for (int o = 0; o < NF; o++) {
+        H1[(o0 + o) * LS + lane] = tanhf(hp[o]);
+        H1[(64 + o0 + o) * LS + lane] = tanhf(hv[o]);
+    }
+}
+// ---- F: policy_net L1 | value_net_body L1: 64 -> 64 each, Tanh: H1 -> H2[128]
+template <int K>
+__device__ __forceinline__ void pol_l1(const float *__restrict__ W, int wv, int lane, const float *H1, float *H2) {
+    constexpr PolBlob L = pol_blob(K);
+    constexpr int LS = POL_LS, NF = POL_NF;
+    float hp[NF], hv[NF];
+    const int o0 = wv * NF;
+#pragma unroll
+    for (int o = 0; o < NF; o++) { hp[o] = W[L.p1_b + o0 + o]; hv[o] = W[L.v1_b + o0 + o]; }
+    pol_dot<NF>(hp, W + L.p1_w + o0 * 64, 64, 64, pol_lds4(H1 + lane));
+    pol_dot<NF>(hv, W + L.v1_w + o0 * 64, 64, 64, pol_lds4(H1 + 64 * LS + lane));
+#pragma unroll
+    for (int o = 0; o < NF; o++) {
+        H2[(o0 + o) * LS + lane] = tanhf(hp[o]);
+        H2[(64 + o0 + o) * LS + lane] = tanhf(hv[o]);
+    }
+}
 
 template <int K>
 __global__ __launch_bounds__(POL_THREADS, 4) void mgx_policy_kernel(PolArgs a) {
@@ -118,222 +347,26 @@ __global__ __launch_bounds__(POL_THREADS, 4) void mgx_policy_kernel(PolArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);          // wave-uniform: weight addresses stay scalar
     const int64_t b0 = (int64_t)blockIdx.x * POL_TILE;
-    const int nb = (int)min<int64_t>(POL_TILE, a.B - b0);
+    const int nb = (int)min<int64_t>(POL_TILE, a.s.B - b0);
     const float *__restrict__ W = a.blob;
 
-    // ---- A: source row and validity of every (sample, slot); slot K-1 is the newest (mgx_gather_kernel's rules)
-    for (int pr = tid; pr < POL_TILE * K; pr += POL_THREADS) {
-        const int bi = pr / K, k = pr - bi * K;
-        const uint8_t *src = nullptr;
-        int mid = -1;
-        if (bi < nb) {
-            const int64_t idx = a.index[b0 + bi];
-            const int64_t row0 = idx / a.N, env = idx - row0 * a.N;
-            const int64_t R = a.R;
-            const auto back_idx = [&](int j) -> int64_t {
-                int64_t r = row0 - j;
-                if (R > 0 && r < 0) r += ((-r + R - 1) / R) * R;
-                return r * a.N + env;
-            };
-            const int back = K - 1 - k;
-            if (a.newest) {
-                if (back == 0) { src = a.newest + env * FROW; mid = a.mids[idx]; }
-                else {
-                    bool ok = true;
-                    for (int j = 0; j < back - 1 && ok; j++) ok = !a.starts[back_idx(j)];
-                    if (ok) { const int64_t r = back_idx(back - 1); src = a.rows + r * FROW; mid = a.mids[r]; }
-                }
-            } else {
-                bool ok = true;
-                for (int j = 0; j < back && ok; j++) ok = !a.starts[back_idx(j)];
-                if (ok) { const int64_t r = back_idx(back); src = a.rows + r * FROW; mid = a.mids[r]; }
-            }
-        }
-        s_src[pr] = src;
-        s_mid[pr] = mid;
-    }
+    pol_stage_src<K>(a.s, a.newest, b0, nb, tid, s_src, s_mid);       // A
     __syncthreads();
-    // ---- A2: stage the rows: X[(k * 37 + w) * 65 + sample] = dword w of slot k
-    {
-        uint32_t *Xu = reinterpret_cast<uint32_t *>(X);
-        for (int i = tid; i < POL_TILE * K * POL_RW; i += POL_THREADS) {
-            const int pr = i / POL_RW, w = i - pr * POL_RW;
-            const int bi = pr / K, k = pr - bi * K;
-            const uint8_t *src = s_src[pr];
-            Xu[(k * POL_RW + w) * LS + bi] = src ? reinterpret_cast<const uint32_t *>(src)[w] : 0u;
-        }
-    }
-    // valid slots are contiguous from the newest and share its mission id: v = their count
-    int v = 0;
-#pragma unroll
-    for (int k = 0; k < K; k++) v += s_mid[lane * K + k] >= 0;
-    const int my_mid = lane < nb ? s_mid[lane * K + K - 1] : 0;
-    const float *__restrict__ mf = a.mfeat + ((size_t)my_mid * K + (v > 0 ? v - 1 : 0)) * 128;
+    pol_stage_rows<K>(s_src, tid, X);                                 // A2
+    int v;
+    const float *__restrict__ mf = a.mfeat + (size_t)pol_feat_row<K>(s_mid, lane, nb, v) * 128;
     __syncthreads();
     const uint8_t *xb = reinterpret_cast<const uint8_t *>(X) + lane * 4;
-
-    uint32_t dsel = 0;                                                // direction (row byte 0) of slot k at bits 2k
-#pragma unroll
-    for (int k = 0; k < K; k++) dsel |= (uint32_t)(xb[(k * POL_RW) * LS * 4] & 3) << (2 * k);
-    // ---- B: conv1 (3K -> 16, 2x2) + ReLU + MaxPool 2: wave = 4 output channels x 5 or 4 of the 9 pooled cells;
-    // per pooled cell the 2x2 conv outputs under it from a 3x3 input patch per channel (16 accumulators, 64 fmaf
-    // per 9 pixels)
-    {
-        const int oc0 = (wv & 3) * 4;
-        const int cell0 = (wv >> 2) ? 5 : 0, cell1 = (wv >> 2) ? 9 : 5;
-        for (int cell = cell0; cell < cell1; cell++) {
-            const int py = cell / 3, px = cell - py * 3;
-            float acc[4][4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const float bq = W[L.c1_b + oc0 + q];
-#pragma unroll
-                for (int p = 0; p < 4; p++) acc[q][p] = bq;
-            }
-#pragma nounroll                       // (at n_stack 2 the 6 trips were unrolled: 284 scalar registers spilled)
-            for (int c = 0; c < 3 * K; c++) {
-                const int k = c / 3, ch = c - k * 3;
-                float pix[9];
-#pragma unroll
-                for (int i = 0; i < 3; i++)
-#pragma unroll
-                    for (int j = 0; j < 3; j++) {
-                        const int bp = 1 + ch * 49 + (2 * py + i) * 7 + 2 * px + j;      // byte of the row
-                        pix[i * 3 + j] = (float)xb[((k * POL_RW + (bp >> 2)) * LS) * 4 + (bp & 3)] * (1.0f / 255.0f);
-                    }
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const float *__restrict__ wq = W + L.c1_w + ((oc0 + q) * 3 * K + c) * 4;
-#pragma unroll
-                    for (int dy = 0; dy < 2; dy++)
-#pragma unroll
-                        for (int dx = 0; dx < 2; dx++) {
-                            const float wt = wq[dy * 2 + dx];
-#pragma unroll
-                            for (int oy = 0; oy < 2; oy++)
-#pragma unroll
-                                for (int ox = 0; ox < 2; ox++)
-                                    acc[q][oy * 2 + ox] = __builtin_fmaf(pix[(oy + dy) * 3 + ox + dx], wt, acc[q][oy * 2 + ox]);
-                        }
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-                P[((oc0 + q) * 9 + cell) * LS + lane] =
-                    fmaxf(fmaxf(fmaxf(acc[q][0], acc[q][1]), fmaxf(acc[q][2], acc[q][3])), 0.0f);
-        }
-    }
+    const uint32_t dsel = pol_dsel<K>(xb);
+    pol_conv1<K>(W, wv, lane, xb, P);                                 // B
     __syncthreads();                                                  // rows dead from here: X becomes C2
-    // ---- C: conv2 (16 -> 32, 2x2 on 3x3) + ReLU: wave = 4 output channels x 4 positions (16 accumulators)
-    {
-        constexpr int NQ = 32 / POL_NW;
-        const int oc0 = wv * NQ;
-        float acc[NQ][4];
-#pragma unroll
-        for (int q = 0; q < NQ; q++) {
-            const float bq = W[L.c2_b + oc0 + q];
-#pragma unroll
-            for (int p = 0; p < 4; p++) acc[q][p] = bq;
-        }
-        for (int ic = 0; ic < 16; ic++) {
-            float in[9];
-#pragma unroll
-            for (int j = 0; j < 9; j++) in[j] = P[(ic * 9 + j) * LS + lane];
-#pragma unroll
-            for (int q = 0; q < NQ; q++) {
-                const float *__restrict__ wq = W + L.c2_w + ((oc0 + q) * 16 + ic) * 4;
-#pragma unroll
-                for (int dy = 0; dy < 2; dy++)
-#pragma unroll
-                    for (int dx = 0; dx < 2; dx++) {
-                        const float wt = wq[dy * 2 + dx];
-#pragma unroll
-                        for (int oy = 0; oy < 2; oy++)
-#pragma unroll
-                            for (int ox = 0; ox < 2; ox++)
-                                acc[q][oy * 2 + ox] = __builtin_fmaf(in[(oy + dy) * 3 + ox + dx], wt, acc[q][oy * 2 + ox]);
-                    }
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < NQ; q++)
-#pragma unroll
-            for (int p = 0; p < 4; p++) X[((oc0 + q) * 4 + p) * LS + lane] = fmaxf(acc[q][p], 0.0f);
-    }
+    pol_conv2<K>(W, wv, lane, P, X);                                  // C
     __syncthreads();
-    // ---- D: conv3 (32 -> 64, 2x2 on 2x2 = a 128 -> 64 dot) + ReLU -> F[16 .. 80): wave = 8 output channels
-    constexpr int NF = 64 / POL_NW;                                   // outputs per wave of a 64-wide layer
-    {
-        const int o0 = wv * NF;
-        float acc[NF];
-#pragma unroll
-        for (int o = 0; o < NF; o++) acc[o] = W[L.c3_b + o0 + o];
-        const float *xin = X + lane;
-        pol_dot<NF>(acc, W + L.c3_w + o0 * 128, 128, 128, [&](int i0, float (&x)[4]) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) x[j] = xin[(i0 + j) * LS];
-        });
-#pragma unroll
-        for (int o = 0; o < NF; o++) F[(16 + o0 + o) * LS + lane] = fmaxf(acc[o], 0.0f);
-        // direction Linear(4K -> 16): bias + one weight column per valid slot (one-hot input); wave = 2 outputs
-#pragma unroll
-        for (int q = 0; q < 16 / POL_NW; q++) {
-            const int o = wv * (16 / POL_NW) + q;
-            float acc1 = W[L.dir_b + o];
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                const float wt = W[L.dir_w + o * 4 * K + 4 * k + ((dsel >> (2 * k)) & 3)];
-                acc1 = __builtin_fmaf(k >= K - v ? 1.0f : 0.0f, wt, acc1);
-            }
-            F[o * LS + lane] = acc1;
-        }
-    }
+    pol_conv3_dir<K>(W, wv, lane, dsel, v, X, F);                     // D
     __syncthreads();
-    // ---- E: policy_net L0 | value_net_body L0: 208 -> 64 each, Tanh; wave = 8 + 8 outputs sharing every input.
-    // Inputs 0..79 from F, 80..207 the (mission, v) feature row, read by each lane from the table (float4)
-    float hp[NF], hv[NF];
-    {
-        const int o0 = wv * NF;
-#pragma unroll
-        for (int o = 0; o < NF; o++) { hp[o] = W[L.p0_b + o0 + o]; hv[o] = W[L.v0_b + o0 + o]; }
-        const float *xin = F + lane;
-        pol_dot2<NF>(hp, hv, W + L.p0_w + o0 * POL_FEAT, W + L.v0_w + o0 * POL_FEAT, POL_FEAT, 80,
-                     [&](int i0, float (&x)[4]) {
-#pragma unroll
-                         for (int j = 0; j < 4; j++) x[j] = xin[(i0 + j) * LS];
-                     });
-        pol_dot2<NF>(hp, hv, W + L.p0_w + o0 * POL_FEAT + 80, W + L.v0_w + o0 * POL_FEAT + 80, POL_FEAT, 128,
-                     [&](int i0, float (&x)[4]) {
-                         const float4 m = *reinterpret_cast<const float4 *>(mf + i0);
-                         x[0] = m.x; x[1] = m.y; x[2] = m.z; x[3] = m.w;
-                     });
-#pragma unroll
-        for (int o = 0; o < NF; o++) {                                // H1 = X: [0..64) policy, [64..128) value
-            X[(o0 + o) * LS + lane] = tanhf(hp[o]);
-            X[(64 + o0 + o) * LS + lane] = tanhf(hv[o]);
-        }
-    }
+    pol_l0<K>(W, wv, lane, mf, F, X);                                 // E: H1 = X
     __syncthreads();
-    // ---- F: policy_net L1 | value_net_body L1: 64 -> 64 each, Tanh -> H2 = P
-    {
-        const int o0 = wv * NF;
-#pragma unroll
-        for (int o = 0; o < NF; o++) { hp[o] = W[L.p1_b + o0 + o]; hv[o] = W[L.v1_b + o0 + o]; }
-        const float *xp = X + lane, *xv = X + 64 * LS + lane;
-        pol_dot<NF>(hp, W + L.p1_w + o0 * 64, 64, 64, [&](int i0, float (&x)[4]) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) x[j] = xp[(i0 + j) * LS];
-        });
-        pol_dot<NF>(hv, W + L.v1_w + o0 * 64, 64, 64, [&](int i0, float (&x)[4]) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) x[j] = xv[(i0 + j) * LS];
-        });
-#pragma unroll
-        for (int o = 0; o < NF; o++) {
-            P[(o0 + o) * LS + lane] = tanhf(hp[o]);
-            P[(64 + o0 + o) * LS + lane] = tanhf(hv[o]);
-        }
-    }
+    pol_l1<K>(W, wv, lane, X, P);                                     // F: H2 = P
     __syncthreads();
     // ---- G: heads, action choice and outputs: wave 0, one sample per lane
     if (wv != 0) return;
@@ -341,17 +374,8 @@ __global__ __launch_bounds__(POL_THREADS, 4) void mgx_policy_kernel(PolArgs a) {
 #pragma unroll
     for (int o = 0; o < POL_NA; o++) lg[o] = W[L.a_b + o];
     val[0] = W[L.vn_b];
-    {
-        const float *xp = P + lane, *xv = P + 64 * LS + lane;
-        pol_dot<POL_NA>(lg, W + L.a_w, 64, 64, [&](int i0, float (&x)[4]) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) x[j] = xp[(i0 + j) * LS];
-        });
-        pol_dot<1>(val, W + L.vn_w, 64, 64, [&](int i0, float (&x)[4]) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) x[j] = xv[(i0 + j) * LS];
-        });
-    }
+    pol_dot<POL_NA>(lg, W + L.a_w, 64, 64, pol_lds4(P + lane));
+    pol_dot<1>(val, W + L.vn_w, 64, 64, pol_lds4(P + 64 * LS + lane));
     unsigned long long c = 0;
     if (a.mode == 2) c = *reinterpret_cast<volatile unsigned long long *>(a.ctr);
     if (lane < nb) {

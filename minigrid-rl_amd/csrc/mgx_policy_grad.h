@@ -7,8 +7,8 @@
 // into its own slab scratch[g][blob words] with plain loads and stores (the first tile stores, so the scratch need
 // not be zeroed); mgx_policy_fold_kernel then adds the slabs in group order: grad_blob is bitwise reproducible.
 // Three passes per tile:
-//   (a) forward   stages A-F of mgx_policy_kernel (a second copy: that kernel's registers stay as they are), every
-//                 activation kept in LDS as [feature][sample], row stride 65 dwords
+//   (a) forward   stages A-F of mgx_policy_kernel: the same pol_* functions (mgx_policy.h) with this kernel's LDS
+//                 regions, every activation kept in LDS as [feature][sample], row stride 65 dwords
 //   (b) backward  lane = sample, waves split a layer's INPUTS: dX[i] = sum_o W[o][i] dZ[o] with wave-uniform scalar
 //                 weight loads, written in place over the activation it replaces (Tanh' and ReLU' from the outputs)
 //   (c) weights   dW[o][i] = sum_s dZ[o][s] A[i][s] on v_mfma_f32_32x32x2_f32 (exact fp32, k = sample ascending):
@@ -33,10 +33,7 @@ constexpr size_t pg_lds_bytes() { return (size_t)PG_ROWS * POL_LS * 4; }
 typedef float pg_f16 __attribute__((ext_vector_type(16)));
 
 struct PolGradArgs {
-    const uint8_t *rows, *mids, *starts;
-    int64_t N, R;
-    const int64_t *index;
-    int64_t B;
+    SampleAddr s;
     const float *blob, *mfeat, *g_logits, *g_values;
     float *gmf, *scratch;
     int groups;
@@ -73,18 +70,18 @@ __global__ __launch_bounds__(POL_THREADS, 2) void mgx_policy_grad_kernel(PolGrad
     extern __shared__ __align__(16) uint8_t smem[];
     constexpr PolBlob L = pol_blob(K);
     constexpr int LS = POL_LS;
-    constexpr int NF = 64 / POL_NW;
+    constexpr int NF = POL_NF;
     float *S = reinterpret_cast<float *>(smem);
     float *P = S + PG_P * LS, *C2 = S + PG_C2 * LS, *F = S + PG_F * LS, *H1 = S + PG_H1 * LS, *H2 = S + PG_H2 * LS;
     float *Y = C2;                                                    // the input rows: [K * 37][65]
     uint8_t *PosB = reinterpret_cast<uint8_t *>(S + PG_POS * LS);
-    int64_t *s_row = reinterpret_cast<int64_t *>(S + PG_IDX * LS);    // [64 * K], -1: empty slot
-    int *s_mid = reinterpret_cast<int *>(s_row + POL_TILE * K);       // [64 * K]
+    const uint8_t **s_src = reinterpret_cast<const uint8_t **>(S + PG_IDX * LS);   // [64 * K], nullptr: empty slot
+    int *s_mid = reinterpret_cast<int *>(s_src + POL_TILE * K);       // [64 * K], -1: empty slot
     __shared__ float s_g[8 * POL_LS];                                 // cotangents: rows 0..6 logits, 7 value
     __shared__ int s_key[POL_TILE];                                   // mid * K + v - 1; -1: spare lane
     __shared__ int s_lead[POL_TILE];                                  // ordinal among the tile's distinct keys, or -1
     float *slab = a.scratch + (size_t)blockIdx.x * L.words;
-    const int64_t ntiles = (a.B + POL_TILE - 1) / POL_TILE;
+    const int64_t ntiles = (a.s.B + POL_TILE - 1) / POL_TILE;
 
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += a.groups) {
         // the thread id is made opaque once per tile: hoisted out of this loop, the per-lane LDS addresses of every
@@ -98,7 +95,7 @@ __global__ __launch_bounds__(POL_THREADS, 2) void mgx_policy_grad_kernel(PolGrad
         const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform: weight addresses stay scalar
         const bool first = tile == (int64_t)blockIdx.x;
         const int64_t b0 = tile * POL_TILE;
-        const int nb = (int)min<int64_t>(POL_TILE, a.B - b0);
+        const int nb = (int)min<int64_t>(POL_TILE, a.s.B - b0);
         // slab[off] (+)= v
         const auto put = [&](int off, float v) { slab[off] = first ? v : slab[off] + v; };
         // sums of `per` consecutive LDS rows over the 64 samples -> n bias gradients: a lane adds its sample's `per`
@@ -112,82 +109,15 @@ __global__ __launch_bounds__(POL_THREADS, 2) void mgx_policy_grad_kernel(PolGrad
                 if (lane == 0) put(off + o, x);
             }
         };
-        // ---- A, A2: source row of every (sample, slot), then the rows -> Y (mgx_policy_kernel's, no terminal rows)
+        // ---- A, A2: source row of every (sample, slot), then the rows -> Y (no terminal rows)
         const auto stage_rows = [&]() {
-            for (int pr = tid; pr < POL_TILE * K; pr += POL_THREADS) {
-                const int bi = pr / K, k = pr - bi * K;
-                int64_t row = -1;
-                int mid = -1;
-                if (bi < nb) {
-                    const int64_t idx = a.index[b0 + bi];
-                    const int64_t row0 = idx / a.N, env = idx - row0 * a.N;
-                    const int64_t R = a.R;
-                    const auto back_idx = [&](int j) -> int64_t {
-                        int64_t r = row0 - j;
-                        if (R > 0 && r < 0) r += ((-r + R - 1) / R) * R;
-                        return r * a.N + env;
-                    };
-                    const int back = K - 1 - k;
-                    bool ok = true;
-                    for (int j = 0; j < back && ok; j++) ok = !a.starts[back_idx(j)];
-                    if (ok) { row = back_idx(back); mid = a.mids[row]; }
-                }
-                s_row[pr] = row;
-                s_mid[pr] = mid;
-            }
+            pol_stage_src<K>(a.s, nullptr, b0, nb, tid, s_src, s_mid);
             __syncthreads();
-            uint32_t *Yu = reinterpret_cast<uint32_t *>(Y);
-            for (int i = tid; i < POL_TILE * K * POL_RW; i += POL_THREADS) {
-                const int pr = i / POL_RW, w = i - pr * POL_RW;
-                const int bi = pr / K, k = pr - bi * K;
-                const int64_t row = s_row[pr];
-                Yu[(k * POL_RW + w) * LS + bi] = row >= 0 ? reinterpret_cast<const uint32_t *>(a.rows + row * FROW)[w] : 0u;
-            }
+            pol_stage_rows<K>(s_src, tid, Y);
         };
-        // conv1's 3x3 input patch under pooled cell (py, px) of channel c, as stage B reads it
         const uint8_t *xb = reinterpret_cast<const uint8_t *>(Y) + lane * 4;
-        const auto patch = [&](int c, int py, int px, float (&pix)[9]) {
-            const int k = c / 3, ch = c - k * 3;
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-#pragma unroll
-                for (int j = 0; j < 3; j++) {
-                    const int bp = 1 + ch * 49 + (2 * py + i) * 7 + 2 * px + j;
-                    pix[i * 3 + j] = (float)xb[((k * POL_RW + (bp >> 2)) * LS) * 4 + (bp & 3)] * (1.0f / 255.0f);
-                }
-        };
-        // conv1's four outputs under pooled cell `cell` for output channels oc0 .. oc0 + 3 (stage B's arithmetic)
-        const auto conv1_cell = [&](int oc0, int cell, float (&acc)[4][4]) {
-            const int py = cell / 3, px = cell - py * 3;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const float bq = W[L.c1_b + oc0 + q];
-#pragma unroll
-                for (int p = 0; p < 4; p++) acc[q][p] = bq;
-            }
-#pragma nounroll
-            for (int c = 0; c < 3 * K; c++) {
-                float pix[9];
-                patch(c, py, px, pix);
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const float *__restrict__ wq = W + L.c1_w + ((oc0 + q) * 3 * K + c) * 4;
-#pragma unroll
-                    for (int dy = 0; dy < 2; dy++)
-#pragma unroll
-                        for (int dx = 0; dx < 2; dx++) {
-                            const float wt = wq[dy * 2 + dx];
-#pragma unroll
-                            for (int oy = 0; oy < 2; oy++)
-#pragma unroll
-                                for (int ox = 0; ox < 2; ox++)
-                                    acc[q][oy * 2 + ox] = __builtin_fmaf(pix[(oy + dy) * 3 + ox + dx], wt, acc[q][oy * 2 + ox]);
-                        }
-                }
-            }
-        };
 
-        // =============================================================== (a) forward
+        // =============================================================== (a) forward: mgx_policy.h's stages
         stage_rows();
         for (int i = tid; i < 8 * POL_TILE; i += POL_THREADS) {      // the cotangents; spare lanes: exactly zero
             const int o = i >> 6, s = i & 63;
@@ -195,11 +125,8 @@ __global__ __launch_bounds__(POL_THREADS, 2) void mgx_policy_grad_kernel(PolGrad
             if (s < nb) g = o < POL_NA ? a.g_logits[(b0 + s) * POL_NA + o] : a.g_values[b0 + s];
             s_g[o * LS + s] = g;
         }
-        int v = 0;
-#pragma unroll
-        for (int k = 0; k < K; k++) v += s_mid[lane * K + k] >= 0;
-        const int my_mid = lane < nb ? s_mid[lane * K + K - 1] : 0;
-        const int my_key = my_mid * K + (v > 0 ? v - 1 : 0);
+        int v;
+        const int my_key = pol_feat_row<K>(s_mid, lane, nb, v);
         const float *__restrict__ mf = a.mfeat + (size_t)my_key * 128;
         if (wv == 0) {                                                // a key's first sample leads its table sum
             const int kreg = lane < nb ? my_key : -1;
@@ -213,131 +140,16 @@ __global__ __launch_bounds__(POL_THREADS, 2) void mgx_policy_grad_kernel(PolGrad
             s_lead[lane] = lead ? __popcll(leaders & ((1ull << lane) - 1ull)) : -1;
         }
         __syncthreads();
-        uint32_t dsel = 0;
-#pragma unroll
-        for (int k = 0; k < K; k++) dsel |= (uint32_t)(xb[(k * POL_RW) * LS * 4] & 3) << (2 * k);
-        // ---- B: conv1 + ReLU + MaxPool -> P
-        {
-            const int oc0 = (wv & 3) * 4;
-            const int cell0 = (wv >> 2) ? 5 : 0, cell1 = (wv >> 2) ? 9 : 5;
-            for (int cell = cell0; cell < cell1; cell++) {
-                float acc[4][4];
-                conv1_cell(oc0, cell, acc);
-#pragma unroll
-                for (int q = 0; q < 4; q++)
-                    P[((oc0 + q) * 9 + cell) * LS + lane] =
-                        fmaxf(fmaxf(fmaxf(acc[q][0], acc[q][1]), fmaxf(acc[q][2], acc[q][3])), 0.0f);
-            }
-        }
+        const uint32_t dsel = pol_dsel<K>(xb);
+        pol_conv1<K>(W, wv, lane, xb, P);                             // B
         __syncthreads();                                              // rows dead: Y becomes C2
-        // ---- C: conv2 + ReLU: P -> C2
-        {
-            constexpr int NQ = 32 / POL_NW;
-            const int oc0 = wv * NQ;
-            float acc[NQ][4];
-#pragma unroll
-            for (int q = 0; q < NQ; q++) {
-                const float bq = W[L.c2_b + oc0 + q];
-#pragma unroll
-                for (int p = 0; p < 4; p++) acc[q][p] = bq;
-            }
-            for (int ic = 0; ic < 16; ic++) {
-                float in[9];
-#pragma unroll
-                for (int j = 0; j < 9; j++) in[j] = P[(ic * 9 + j) * LS + lane];
-#pragma unroll
-                for (int q = 0; q < NQ; q++) {
-                    const float *__restrict__ wq = W + L.c2_w + ((oc0 + q) * 16 + ic) * 4;
-#pragma unroll
-                    for (int dy = 0; dy < 2; dy++)
-#pragma unroll
-                        for (int dx = 0; dx < 2; dx++) {
-                            const float wt = wq[dy * 2 + dx];
-#pragma unroll
-                            for (int oy = 0; oy < 2; oy++)
-#pragma unroll
-                                for (int ox = 0; ox < 2; ox++)
-                                    acc[q][oy * 2 + ox] = __builtin_fmaf(in[(oy + dy) * 3 + ox + dx], wt, acc[q][oy * 2 + ox]);
-                        }
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < NQ; q++)
-#pragma unroll
-                for (int p = 0; p < 4; p++) C2[((oc0 + q) * 4 + p) * LS + lane] = fmaxf(acc[q][p], 0.0f);
-        }
+        pol_conv2<K>(W, wv, lane, P, C2);                             // C
         __syncthreads();
-        // ---- D: conv3 + ReLU -> F[16..80); direction Linear -> F[0..16)
-        {
-            const int o0 = wv * NF;
-            float acc[NF];
-#pragma unroll
-            for (int o = 0; o < NF; o++) acc[o] = W[L.c3_b + o0 + o];
-            const float *xin = C2 + lane;
-            pol_dot<NF>(acc, W + L.c3_w + o0 * 128, 128, 128, [&](int i0, float (&x)[4]) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) x[j] = xin[(i0 + j) * LS];
-            });
-#pragma unroll
-            for (int o = 0; o < NF; o++) F[(16 + o0 + o) * LS + lane] = fmaxf(acc[o], 0.0f);
-#pragma unroll
-            for (int q = 0; q < 16 / POL_NW; q++) {
-                const int o = wv * (16 / POL_NW) + q;
-                float acc1 = W[L.dir_b + o];
-#pragma unroll
-                for (int k = 0; k < K; k++) {
-                    const float wt = W[L.dir_w + o * 4 * K + 4 * k + ((dsel >> (2 * k)) & 3)];
-                    acc1 = __builtin_fmaf(k >= K - v ? 1.0f : 0.0f, wt, acc1);
-                }
-                F[o * LS + lane] = acc1;
-            }
-        }
+        pol_conv3_dir<K>(W, wv, lane, dsel, v, C2, F);                // D
         __syncthreads();
-        // ---- E: policy_net L0 | value_net_body L0 -> H1
-        {
-            float hp[NF], hv[NF];
-            const int o0 = wv * NF;
-#pragma unroll
-            for (int o = 0; o < NF; o++) { hp[o] = W[L.p0_b + o0 + o]; hv[o] = W[L.v0_b + o0 + o]; }
-            const float *xin = F + lane;
-            pol_dot2<NF>(hp, hv, W + L.p0_w + o0 * POL_FEAT, W + L.v0_w + o0 * POL_FEAT, POL_FEAT, 80,
-                         [&](int i0, float (&x)[4]) {
-#pragma unroll
-                             for (int j = 0; j < 4; j++) x[j] = xin[(i0 + j) * LS];
-                         });
-            pol_dot2<NF>(hp, hv, W + L.p0_w + o0 * POL_FEAT + 80, W + L.v0_w + o0 * POL_FEAT + 80, POL_FEAT, 128,
-                         [&](int i0, float (&x)[4]) {
-                             const float4 m = *reinterpret_cast<const float4 *>(mf + i0);
-                             x[0] = m.x; x[1] = m.y; x[2] = m.z; x[3] = m.w;
-                         });
-#pragma unroll
-            for (int o = 0; o < NF; o++) {
-                H1[(o0 + o) * LS + lane] = tanhf(hp[o]);
-                H1[(64 + o0 + o) * LS + lane] = tanhf(hv[o]);
-            }
-        }
+        pol_l0<K>(W, wv, lane, mf, F, H1);                            // E
         __syncthreads();
-        // ---- F: policy_net L1 | value_net_body L1 -> H2
-        {
-            float hp[NF], hv[NF];
-            const int o0 = wv * NF;
-#pragma unroll
-            for (int o = 0; o < NF; o++) { hp[o] = W[L.p1_b + o0 + o]; hv[o] = W[L.v1_b + o0 + o]; }
-            const float *xp = H1 + lane, *xv = H1 + 64 * LS + lane;
-            pol_dot<NF>(hp, W + L.p1_w + o0 * 64, 64, 64, [&](int i0, float (&x)[4]) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) x[j] = xp[(i0 + j) * LS];
-            });
-            pol_dot<NF>(hv, W + L.v1_w + o0 * 64, 64, 64, [&](int i0, float (&x)[4]) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) x[j] = xv[(i0 + j) * LS];
-            });
-#pragma unroll
-            for (int o = 0; o < NF; o++) {
-                H2[(o0 + o) * LS + lane] = tanhf(hp[o]);
-                H2[(64 + o0 + o) * LS + lane] = tanhf(hv[o]);
-            }
-        }
+        pol_l1<K>(W, wv, lane, H1, H2);                               // F
         __syncthreads();
 
         // =============================================================== (b), (c) backward, heads first
@@ -553,11 +365,11 @@ __global__ __launch_bounds__(POL_THREADS, 2) void mgx_policy_grad_kernel(PolGrad
         stage_rows();
         __syncthreads();
         {
-            const int oc0 = (wv & 3) * 4;
-            const int cell0 = (wv >> 2) ? 5 : 0, cell1 = (wv >> 2) ? 9 : 5;
+            int oc0, cell0, cell1;
+            pol_conv1_share(wv, oc0, cell0, cell1);
             for (int cell = cell0; cell < cell1; cell++) {
                 float acc[4][4];
-                conv1_cell(oc0, cell, acc);
+                pol_conv1_cell<K>(W, xb, oc0, cell, acc);
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     int pos = 0;
@@ -583,7 +395,7 @@ __global__ __launch_bounds__(POL_THREADS, 2) void mgx_policy_grad_kernel(PolGrad
                 for (int cell = 0; cell < 9; cell++) {
                     const int py = cell / 3, px = cell - py * 3;
                     float pix[9];
-                    patch(c, py, px, pix);
+                    pol_conv1_patch(xb, c, py, px, pix);
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
                         const int idx = (oc0 + q) * 9 + cell;

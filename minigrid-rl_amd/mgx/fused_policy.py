@@ -134,6 +134,27 @@ def mission_table(policy, tokens=None):
     return out.to(torch.float32).reshape(256, k, 128).contiguous()
 
 
+def library_blob_words(engine, n_stack):
+    """mgx_policy_blob_words(n_stack); MgxError unless the packer's layout has as many words."""
+    words = int(engine.L.mgx_policy_blob_words(n_stack))
+    if words != blob_words(n_stack):
+        raise _lib.MgxError("blob layout mismatch: library %d words, packer %d" % (words, blob_words(n_stack)))
+    return words
+
+
+def sample_addr(engine, buf, index, terminal=None):
+    """The leading arguments of mgx_policy_act / mgx_policy_backward: (handle, rows, mids, starts, N, ring_rows,
+    index, n).  terminal False / True appends mgx_policy_act's terminal_rows (null / the buffer's)."""
+    if buf.engine is not engine:
+        raise ValueError("the buffer belongs to another engine")
+    P = ctypes.c_void_p
+    addr = (engine.h, P(buf.rows.data_ptr()), P(buf.mids.data_ptr()), P(buf.starts.data_ptr()), buf.N,
+            buf.R if buf.ring else 0, P(index.data_ptr()), index.numel())
+    if terminal is None:
+        return addr
+    return addr + (P(buf.terminal_rows.data_ptr()) if terminal else None,)
+
+
 class FusedActor:
     """actions / values / log-probs of `policy` for observations of a CompactBuffer of `engine`, one launch each."""
 
@@ -145,9 +166,7 @@ class FusedActor:
         self.K = k
         self.seed = int(seed) & (2 ** 64 - 1)
         dev = engine.device
-        words = int(engine.L.mgx_policy_blob_words(k))
-        if words != blob_words(k):
-            raise _lib.MgxError("blob layout mismatch: library %d words, packer %d" % (words, blob_words(k)))
+        words = library_blob_words(engine, k)
         self.blob = torch.zeros(words, dtype=torch.float32, device=dev)
         self.mission_feat = torch.zeros((256, k, 128), dtype=torch.float32, device=dev)
         self.counter = torch.zeros(2, dtype=torch.int64, device=dev)      # u64 [2] (mgx_random_actions' contract)
@@ -193,11 +212,8 @@ class FusedActor:
         o.values_dev = values.data_ptr()
         o.log_probs_dev = None if log_probs is None else log_probs.data_ptr()
         o.logits_dev = None if lg is None else lg.data_ptr()
-        P = ctypes.c_void_p
-        _lib.check(e.L.mgx_policy_act(e.h, P(buf.rows.data_ptr()), P(buf.mids.data_ptr()), P(buf.starts.data_ptr()),
-                                      buf.N, buf.R if buf.ring else 0, P(idx.data_ptr()), n,
-                                      P(buf.terminal_rows.data_ptr()) if terminal else None,
-                                      ctypes.byref(p), ctypes.byref(o), e._stream()), "mgx_policy_act")
+        _lib.check(e.L.mgx_policy_act(*sample_addr(e, buf, idx, bool(terminal)), ctypes.byref(p), ctypes.byref(o),
+                                      e._stream()), "mgx_policy_act")
         return actions, values, log_probs, lg
 
     def _index(self, buf, t, envs):

@@ -19,7 +19,7 @@ import ctypes
 import torch
 
 from . import _lib
-from .fused_policy import N_ACTIONS, _params, blob_words, mission_token_stacks
+from .fused_policy import N_ACTIONS, _params, library_blob_words, mission_token_stacks, sample_addr
 
 
 def differentiable_blob(tensors):
@@ -76,9 +76,7 @@ class FusedEvaluator:
             raise ValueError("policy n_stack %d does not match the engine's" % k)
         self.policy, self.engine, self.K = policy, engine, k
         self.max_groups = int(max_groups)
-        self.words = int(engine.L.mgx_policy_blob_words(k))
-        if self.words != blob_words(k):
-            raise _lib.MgxError("blob layout mismatch: library %d words, packer %d" % (self.words, blob_words(k)))
+        self.words = library_blob_words(engine, k)
         self._stacks_all = mission_token_stacks(k, _lib.mission_tokens()).reshape(256 * k, 32 * k)
         self.mission = None
         if fused_mission:
@@ -102,14 +100,6 @@ class FusedEvaluator:
         _, tensors = _params(self.policy)
         return differentiable_blob(tensors), mission_table_rows(self.policy, self._rows, self._stacks, self.mission)
 
-    def _addr(self, buf, index):
-        e = self.engine
-        if buf.engine is not e:
-            raise ValueError("the buffer belongs to another engine")
-        P = ctypes.c_void_p
-        return (e.h, P(buf.rows.data_ptr()), P(buf.mids.data_ptr()), P(buf.starts.data_ptr()), buf.N,
-                buf.R if buf.ring else 0, P(index.data_ptr()), index.numel())
-
     def forward_raw(self, buf, index, blob, mission_feat):
         """mgx_policy_act mode 0 -> (logits f32 [B, 7], values f32 [B])."""
         e, n = self.engine, index.numel()
@@ -119,7 +109,7 @@ class FusedEvaluator:
         p.blob_dev, p.mission_feat_dev, p.mode = blob.data_ptr(), mission_feat.data_ptr(), 0
         o.actions_dev = o.log_probs_dev = None
         o.values_dev, o.logits_dev = values.data_ptr(), logits.data_ptr()
-        _lib.check(e.L.mgx_policy_act(*self._addr(buf, index), None, ctypes.byref(p), ctypes.byref(o), e._stream()),
+        _lib.check(e.L.mgx_policy_act(*sample_addr(e, buf, index, False), ctypes.byref(p), ctypes.byref(o), e._stream()),
                    "mgx_policy_act")
         return logits, values
 
@@ -149,7 +139,7 @@ class FusedEvaluator:
         g.grad_blob_dev, g.grad_mission_feat_dev = gb.data_ptr(), gm.data_ptr()
         g.scratch_dev, g.scratch_words = scratch.data_ptr(), scratch.numel()
         g.max_groups, g.reserved0 = self.max_groups, 0
-        _lib.check(e.L.mgx_policy_backward(*self._addr(buf, index), ctypes.byref(g), e._stream()),
+        _lib.check(e.L.mgx_policy_backward(*sample_addr(e, buf, index), ctypes.byref(g), e._stream()),
                    "mgx_policy_backward")
         return gb, gm
 
