@@ -294,6 +294,40 @@ mgx_status mgx_policy_act(const mgx_handle *h, const uint8_t *rows_dev, const ui
                           int64_t n_samples, const uint8_t *terminal_rows_dev, const mgx_policy *pol,
                           const mgx_act_out *out, void *stream);
 
+/* ---- Truncation bootstrap on the device (added within ABI 9) ---------------------------------------
+ * SB3's `rewards[idx] += gamma * V(terminal_observation)` for every env with truncated & !terminated at one
+ * step of a compact buffer, the work list built on the device: what
+ *    boot = (truncated & ~terminated).nonzero();  r[boot] = r[boot] + gamma * V
+ * computes with V = mgx_policy_act (mode 0, terminal_rows_dev) on the samples row * n_envs + boot -- bit for bit
+ * (the multiply and the add are two fp32 operations), with no host decision, so a captured graph can hold it.
+ * Two launches: (1) one workgroup compacts the selected envs in ascending order into list_dev (flat indices
+ * row * n_envs + e, nonzero()'s order) and writes count_dev; every entry below the count and the count are
+ * written, so neither needs zeroing, and both stay readable afterwards; (2) a grid of ceil(n_envs / 64)
+ * workgroups, one per possible tile of 64 list entries, reads the count on the device: mgx_policy_act's
+ * forward pass and value head on each listed env's terminal stack, then the reward update; a workgroup past
+ * the count exits after that one load.  Deterministic (no float atomics); with nothing selected launch 2
+ * stores nothing and rewards_dev is untouched. */
+typedef struct mgx_bootstrap {
+    const uint8_t *truncated_dev;   /* u8 [n_envs]: this step's flags */
+    const uint8_t *terminated_dev;  /* u8 [n_envs] */
+    float *rewards_dev;             /* f32 [n_envs]: r[e] = r[e] + gamma * V(e) where selected, else untouched */
+    float gamma;
+    int32_t reserved0;              /* 0 */
+    int64_t *list_dev;              /* i64 [n_envs], caller-owned scratch: the selected samples' flat indices */
+    int32_t *count_dev;             /* i32 [1], caller-owned: the number selected */
+    float *values_dev;              /* optional f32 [n_envs]: V of list entry j at [j] */
+} mgx_bootstrap;
+
+/* rows_dev .. ring_rows, terminal_rows_dev: mgx_policy_act's sample addressing; row = the buffer row of the
+ * observation the step left (the terminal stack's older frames start there).  pol: blob_dev and
+ * mission_feat_dev are read (mode, seed and counter_dev are not).  Only enqueues on `stream` (no allocation,
+ * no host sync; capturable).  MGX_ERR_INVALID before any HIP call for: a null pointer (values_dev aside),
+ * n_envs <= 0, row < 0 or, in a ring, row >= ring_rows, 0 < ring_rows < n_stack. */
+mgx_status mgx_policy_bootstrap(const mgx_handle *h, const uint8_t *rows_dev, const uint8_t *mission_ids_dev,
+                                const uint8_t *starts_dev, int64_t n_envs, int64_t ring_rows, int64_t row,
+                                const uint8_t *terminal_rows_dev, const mgx_policy *pol, const mgx_bootstrap *b,
+                                void *stream);
+
 /* ---- Fused policy gradient over compact rows (ABI 9) ---------------------------------------------
  * The backward pass of the network above for the same kind of samples, for the PPO update: given the
  * cotangents of action_net's and value_net's outputs it recomputes the forward pass from the compact rows

@@ -3246,6 +3246,9 @@ mgx_status mgx_create(const mgx_config *cfg, int device, mgx_handle **out) {
         pol_lds = hipFuncSetAttribute((const void *)mgx_policy_kernel<KK>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)pol_lds_bytes(KK));
         if (pol_lds == hipSuccess)
+            pol_lds = hipFuncSetAttribute((const void *)mgx_policy_boot_kernel<KK>,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)pol_lds_bytes(KK));
+        if (pol_lds == hipSuccess)
             pol_grad_lds = hipFuncSetAttribute((const void *)mgx_policy_grad_kernel<KK>,
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)pg_lds_bytes());
     });
@@ -3855,6 +3858,43 @@ mgx_status mgx_policy_act(const mgx_handle *h, const uint8_t *rows_dev, const ui
                            (hipStream_t)stream, a);
     });
     if (!launched) return fail(MGX_ERR_INVALID, "mgx_policy_act: n_stack out of range");
+    HIP_TRY(hipGetLastError());
+    return MGX_OK;
+}
+
+mgx_status mgx_policy_bootstrap(const mgx_handle *h, const uint8_t *rows_dev, const uint8_t *mission_ids_dev,
+                                const uint8_t *starts_dev, int64_t n_envs, int64_t ring_rows, int64_t row,
+                                const uint8_t *terminal_rows_dev, const mgx_policy *pol, const mgx_bootstrap *b,
+                                void *stream) {
+    if (!pol || !b) return fail(MGX_ERR_INVALID, "mgx_policy_bootstrap: null policy / bootstrap arguments");
+    if (!pol->blob_dev || !pol->mission_feat_dev)
+        return fail(MGX_ERR_INVALID, "mgx_policy_bootstrap: null blob / mission features");
+    if (!h || !rows_dev || !mission_ids_dev || !starts_dev || !terminal_rows_dev || !b->truncated_dev ||
+        !b->terminated_dev || !b->rewards_dev || !b->list_dev || !b->count_dev)
+        return fail(MGX_ERR_INVALID, "mgx_policy_bootstrap: null argument");
+    if (n_envs <= 0) return fail(MGX_ERR_INVALID, "mgx_policy_bootstrap: n_envs must be > 0");
+    if (ring_rows < 0 || row < 0 || (ring_rows > 0 && row >= ring_rows))
+        return fail(MGX_ERR_INVALID, "mgx_policy_bootstrap: row outside the buffer");
+    if (ring_rows > 0 && ring_rows < h->kp.n_stack)
+        return fail(MGX_ERR_INVALID, "mgx_policy_bootstrap: the ring must hold n_stack rows");
+    PolBootArgs a;
+    a.rows = rows_dev; a.mids = mission_ids_dev; a.starts = starts_dev;
+    a.N = n_envs; a.R = ring_rows; a.row = row;
+    a.newest = terminal_rows_dev;
+    a.blob = pol->blob_dev; a.mfeat = pol->mission_feat_dev;
+    a.truncated = b->truncated_dev; a.terminated = b->terminated_dev;
+    a.rewards = b->rewards_dev; a.gamma = b->gamma;
+    a.list = b->list_dev; a.count = b->count_dev; a.values = b->values_dev;
+    const int K = h->kp.n_stack;
+    if (K < 1 || K > MAX_NSTACK) return fail(MGX_ERR_INVALID, "mgx_policy_bootstrap: n_stack out of range");
+    hipLaunchKernelGGL(mgx_boot_list_kernel, dim3(1), dim3(BOOT_THREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    const unsigned groups = (unsigned)((n_envs + POL_TILE - 1) / POL_TILE);   // the count is known on the device only
+    for_n_stack(K, [&](auto kk) {
+        constexpr int KK = decltype(kk)::value;
+        hipLaunchKernelGGL(mgx_policy_boot_kernel<KK>, dim3(groups), dim3(POL_THREADS), pol_lds_bytes(KK),
+                           (hipStream_t)stream, a);
+    });
     HIP_TRY(hipGetLastError());
     return MGX_OK;
 }

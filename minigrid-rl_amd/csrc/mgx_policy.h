@@ -424,4 +424,102 @@ __global__ __launch_bounds__(POL_THREADS, 4) void mgx_policy_kernel(PolArgs a) {
     }
 }
 
+// ---- mgx_policy_bootstrap: rewards[e] += gamma * V(terminal observation of e) for every env with truncated & !terminated
+// at one step, the work list built on the device (DESIGN.md "Graph-captured collect").  Two launches.
+struct PolBootArgs {
+    const uint8_t *rows, *mids, *starts;
+    int64_t N, R, row;                     // sample of env e: flat index row * N + e
+    const uint8_t *newest;                 // the terminal rows [N][FROW]
+    const float *blob, *mfeat;
+    const uint8_t *truncated, *terminated;
+    float *rewards;
+    float gamma;
+    int64_t *list;                         // [N]: flat indices of the selected envs, ascending env
+    int *count;                            // [1]
+    float *values;                         // optional [N]: V of list entry j at [j]
+};
+
+// Launch 1: ordered compaction by ONE workgroup: per chunk of BOOT_THREADS envs a ballot per wave, popcounts below
+// the lane, an exclusive scan of the wave totals in LDS.  Entry j of the list is the j-th selected env in ascending
+// order (torch's nonzero()); every list entry below the count and the count itself are written, nothing is read back.
+constexpr int BOOT_THREADS = 1024;
+__global__ __launch_bounds__(BOOT_THREADS) void mgx_boot_list_kernel(PolBootArgs a) {
+    constexpr int NWV = BOOT_THREADS / 64;
+    __shared__ int s_tot[NWV];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int base = 0;                                                     // selected envs before this chunk (uniform)
+    for (int64_t e0 = 0; e0 < a.N; e0 += BOOT_THREADS) {
+        const int64_t e = e0 + tid;
+        const bool sel = e < a.N && a.truncated[e] != 0 && a.terminated[e] == 0;
+        const unsigned long long m = __ballot(sel);
+        if (lane == 0) s_tot[wv] = __popcll(m);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < NWV; w++) {
+            const int c = s_tot[w];
+            before += w < wv ? c : 0;
+            total += c;
+        }
+        if (sel) a.list[base + before + __popcll(m & ((1ull << lane) - 1ull))] = a.row * a.N + e;
+        base += total;
+        __syncthreads();                                              // s_tot is rewritten by the next chunk
+    }
+    if (tid == 0) *a.count = base;
+}
+
+// Launch 2: the value pass over the list: mgx_policy_kernel's stages A to F and the value head on the terminal stack of
+// every listed sample, then rewards[e] = rewards[e] + gamma * v as two fp32 operations (what the eager index_put_ of
+// r[boot] + gamma * V computes).  The count is read from the device, so the grid is sized for the worst case, one
+// workgroup per tile of the N envs; a workgroup whose tile lies past the count exits after that one load, and with count
+// 0 nothing is stored.  One tile per workgroup, as mgx_policy_kernel: with a loop over tiles around the stages the
+// compiler hoists the weight loads out of it (95..127 VGPRs, 20 spilled SGPRs, scratch at n_stack 2).
+template <int K>
+__global__ __launch_bounds__(POL_THREADS, 4) void mgx_policy_boot_kernel(PolBootArgs a) {
+    extern __shared__ __align__(16) uint8_t smem[];
+    constexpr PolBlob L = pol_blob(K);
+    constexpr int LS = POL_LS;
+    float *X = reinterpret_cast<float *>(smem);                       // [pol_x_rows][65]
+    float *P = X + pol_x_rows(K) * LS;                                // [144][65]
+    float *F = P;
+    __shared__ const uint8_t *s_src[POL_TILE * K];
+    __shared__ int s_mid[POL_TILE * K];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const float *__restrict__ W = a.blob;
+    const int64_t cnt = min<int64_t>(*a.count, a.N);                  // (a list never holds more than N entries)
+    const int64_t b0 = (int64_t)blockIdx.x * POL_TILE;
+    if (b0 >= cnt) return;                                            // the whole workgroup: no barrier is skipped
+    const SampleAddr s{a.rows, a.mids, a.starts, a.N, a.R, a.list, cnt};
+    const int nb = (int)min<int64_t>(POL_TILE, cnt - b0);
+    pol_stage_src<K>(s, a.newest, b0, nb, tid, s_src, s_mid);         // A
+    __syncthreads();
+    pol_stage_rows<K>(s_src, tid, X);                                 // A2
+    int v;
+    const float *__restrict__ mf = a.mfeat + (size_t)pol_feat_row<K>(s_mid, lane, nb, v) * 128;
+    __syncthreads();
+    const uint8_t *xb = reinterpret_cast<const uint8_t *>(X) + lane * 4;
+    const uint32_t dsel = pol_dsel<K>(xb);
+    pol_conv1<K>(W, wv, lane, xb, P);                                 // B
+    __syncthreads();
+    pol_conv2<K>(W, wv, lane, P, X);                                  // C
+    __syncthreads();
+    pol_conv3_dir<K>(W, wv, lane, dsel, v, X, F);                     // D
+    __syncthreads();
+    pol_l0<K>(W, wv, lane, mf, F, X);                                 // E
+    __syncthreads();
+    pol_l1<K>(W, wv, lane, X, P);                                     // F
+    __syncthreads();
+    if (wv != 0) return;                                              // the value head: wave 0, one sample per lane
+    float val[1];
+    val[0] = W[L.vn_b];
+    pol_dot<1>(val, W + L.vn_w, 64, 64, pol_lds4(P + 64 * LS + lane));
+    if (lane < nb) {
+        const int64_t e = a.list[b0 + lane] % a.N;
+        const float gv = __fmul_rn(a.gamma, val[0]);
+        a.rewards[e] = __fadd_rn(a.rewards[e], gv);
+        if (a.values) a.values[b0 + lane] = val[0];
+    }
+}
+
 #endif  // MGX_POLICY_H_

@@ -28,7 +28,7 @@ EXPORTS = ("mgx_last_error", "mgx_abi_version", "mgx_create", "mgx_destroy", "mg
            "mgx_step_compact", "mgx_rollout_compact", "mgx_rollout_compact_gae", "mgx_observe_compact", "mgx_gather",
            "mgx_gather_ring", "mgx_scene", "mgx_set_clock", "mgx_clock_words", "mgx_clock_groups",
            "mgx_ring_levels", "mgx_random_actions", "mgx_set_random_policy", "mgx_policy_blob_words",
-           "mgx_policy_act", "mgx_policy_grad_scratch_words", "mgx_policy_backward",
+           "mgx_policy_act", "mgx_policy_bootstrap", "mgx_policy_grad_scratch_words", "mgx_policy_backward",
            "mgx_mission_workspace_words", "mgx_mission_forward", "mgx_mission_backward",
            "mgx_ppo_loss_scratch_words", "mgx_ppo_loss", "mgx_adam_scratch_words", "mgx_adam_step")
 CLOCK_CLASSES = 4   # == MGX_CLOCK_CLASSES (include/mgx.h)
@@ -98,6 +98,14 @@ class MgxActOut(ctypes.Structure):
     _fields_ = [
         ("actions_dev", ctypes.c_void_p), ("values_dev", ctypes.c_void_p), ("log_probs_dev", ctypes.c_void_p),
         ("logits_dev", ctypes.c_void_p),
+    ]
+
+
+class MgxBootstrap(ctypes.Structure):
+    _fields_ = [
+        ("truncated_dev", ctypes.c_void_p), ("terminated_dev", ctypes.c_void_p), ("rewards_dev", ctypes.c_void_p),
+        ("gamma", ctypes.c_float), ("reserved0", ctypes.c_int32), ("list_dev", ctypes.c_void_p),
+        ("count_dev", ctypes.c_void_p), ("values_dev", ctypes.c_void_p),
     ]
 
 
@@ -183,6 +191,8 @@ def load():
     L.mgx_policy_blob_words.argtypes = [I]
     L.mgx_policy_blob_words.restype = I64
     L.mgx_policy_act.argtypes = [P, P, P, P, I64, I64, P, I64, P, ctypes.POINTER(MgxPolicy), ctypes.POINTER(MgxActOut), P]
+    L.mgx_policy_bootstrap.argtypes = [P, P, P, P, I64, I64, I64, P, ctypes.POINTER(MgxPolicy),
+                                       ctypes.POINTER(MgxBootstrap), P]
     L.mgx_policy_grad_scratch_words.argtypes = [I, I64, I]
     L.mgx_policy_grad_scratch_words.restype = I64
     L.mgx_policy_backward.argtypes = [P, P, P, P, I64, I64, P, I64, ctypes.POINTER(MgxPolicyGrad), P]

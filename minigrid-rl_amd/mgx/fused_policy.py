@@ -178,6 +178,10 @@ class FusedActor:
             self._stacks = mission_token_stacks(k, self._tokens).reshape(256 * k, 32 * k).to(torch.uint8).to(dev)
         self._pol = _lib.MgxPolicy()
         self._out = _lib.MgxActOut()
+        self._boot = _lib.MgxBootstrap()
+        self.boot_list = torch.zeros(engine.n, dtype=torch.int64, device=dev)     # bootstrap()'s device work list
+        self.boot_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._table = None                          # index_table()
         self.sync()
 
     @torch.no_grad()
@@ -192,16 +196,31 @@ class FusedActor:
             self.mission_feat.copy_(mission_table(self.policy, self._tokens))
         self.policy.train(was)
 
-    def _run(self, buf, index, mode, terminal=False, logits=False):
+    def _check_out(self, t, n, dtype, what):
+        if t.dtype != dtype or t.numel() != n or not t.is_contiguous() or t.device != self.engine.device:
+            raise ValueError("out: %s must be a contiguous %s tensor of %d elements on %s"
+                             % (what, dtype, n, self.engine.device))
+        return t
+
+    def _run(self, buf, index, mode, terminal=False, logits=False, out=None):
+        """out: (actions, values, log_probs) tensors the kernel writes instead of fresh ones (actions and log_probs
+        None in mode 0)."""
         e = self.engine
         if buf.engine is not e:
             raise ValueError("the buffer belongs to another engine")
         idx = index.to(torch.int64).contiguous()
         n = idx.numel()
         f32 = dict(dtype=torch.float32, device=e.device)
-        values = torch.empty(n, **f32)
-        actions = torch.empty(n, dtype=torch.int64, device=e.device) if mode else None
-        log_probs = torch.empty(n, **f32) if mode else None
+        if out is not None:
+            actions, values, log_probs = out
+            self._check_out(values, n, torch.float32, "values")
+            if mode:
+                self._check_out(actions, n, torch.int64, "actions")
+                self._check_out(log_probs, n, torch.float32, "log_probs")
+        else:
+            values = torch.empty(n, **f32)
+            actions = torch.empty(n, dtype=torch.int64, device=e.device) if mode else None
+            log_probs = torch.empty(n, **f32) if mode else None
         lg = torch.empty((n, N_ACTIONS), **f32) if logits else None
         if n == 0:
             return actions, values, log_probs, lg
@@ -216,19 +235,59 @@ class FusedActor:
                                       e._stream()), "mgx_policy_act")
         return actions, values, log_probs, lg
 
+    def index_table(self, buf):
+        """i64 [R, N]: row r holds the flat indices r * N + env of every env.  Once made for `buf`, act / values
+        over all envs take their index from it (a view, no kernel): what a captured collect uses."""
+        if self._table is None or self._table[0] is not buf:
+            tab = torch.arange(buf.R * buf.N, dtype=torch.int64, device=self.engine.device).view(buf.R, buf.N)
+            self._table = (buf, tab)
+        return self._table[1]
+
     def _index(self, buf, t, envs):
+        if envs is None and self._table is not None and self._table[0] is buf and isinstance(t, int):
+            return self._table[1][buf.row(t)]
         return buf.index(t, buf._arange if envs is None else envs.to(torch.int64))
 
-    def act(self, buf, t, deterministic=False, envs=None, logits=False):
+    def act(self, buf, t, deterministic=False, envs=None, logits=False, out=None):
         """(actions i64 [N], values f32 [N], log_probs f32 [N]) for observation t of `buf` -- what
         policy.forward(buf.gather_step(t), deterministic) returns, sampling aside (own stream).
-        logits=True appends the action_net output f32 [N, 7]."""
-        a, v, lp, lg = self._run(buf, self._index(buf, t, envs), 1 if deterministic else 2, logits=logits)
+        logits=True appends the action_net output f32 [N, 7].  out=(actions, values, log_probs): the kernel writes
+        these tensors (e.g. row t of the rollout arrays) and they are what is returned."""
+        a, v, lp, lg = self._run(buf, self._index(buf, t, envs), 1 if deterministic else 2, logits=logits, out=out)
         return (a, v, lp, lg) if logits else (a, v, lp)
 
-    def values(self, buf, t, terminal=False, envs=None):
-        """policy.predict_values(buf.gather_step(t, terminal=terminal, envs=envs))."""
-        return self._run(buf, self._index(buf, t, envs), 0, terminal=terminal)[1]
+    def values(self, buf, t, terminal=False, envs=None, out=None):
+        """policy.predict_values(buf.gather_step(t, terminal=terminal, envs=envs)); out: the f32 tensor to write."""
+        return self._run(buf, self._index(buf, t, envs), 0, terminal=terminal,
+                         out=None if out is None else (None, out, None))[1]
+
+    def bootstrap(self, buf, t, gamma, rewards=None, values=None):
+        """SB3's truncation bootstrap of step t on the device (mgx_policy_bootstrap): rewards[e] = rewards[e] +
+        f32(gamma) * V(terminal observation of e) for every env with truncated & ~terminated at step t, in place in
+        `rewards` (default buf.rewards[t]) -- no host read, so a captured graph can hold it.  Afterwards
+        self.boot_count (i32 [1]) is the number of such envs and self.boot_list[:count] their flat indices
+        (ascending env); values: optional f32 [N], V of list entry j at [j]."""
+        e = self.engine
+        if buf.engine is not e:
+            raise ValueError("the buffer belongs to another engine")
+        n = buf.N
+        r = buf.rewards[t] if rewards is None else rewards
+        self._check_out(r, n, torch.float32, "rewards")
+        if values is not None:
+            self._check_out(values, n, torch.float32, "values")
+        p, b = self._pol, self._boot
+        p.blob_dev, p.mission_feat_dev = self.blob.data_ptr(), self.mission_feat.data_ptr()
+        p.mode, p.seed, p.counter_dev = 0, self.seed, self.counter.data_ptr()
+        b.truncated_dev, b.terminated_dev = buf.truncated[t].data_ptr(), buf.terminated[t].data_ptr()
+        b.rewards_dev, b.gamma = r.data_ptr(), float(gamma)
+        b.list_dev, b.count_dev = self.boot_list.data_ptr(), self.boot_count.data_ptr()
+        b.values_dev = None if values is None else values.data_ptr()
+        P = ctypes.c_void_p
+        _lib.check(e.L.mgx_policy_bootstrap(e.h, P(buf.rows.data_ptr()), P(buf.mids.data_ptr()),
+                                            P(buf.starts.data_ptr()), n, buf.R if buf.ring else 0, int(buf.row(t)),
+                                            P(buf.terminal_rows.data_ptr()), ctypes.byref(p), ctypes.byref(b),
+                                            e._stream()), "mgx_policy_bootstrap")
+        return r
 
     def logits(self, buf, t, terminal=False, envs=None):
         """(logits f32 [N, 7], values f32 [N]) of observation t (tests)."""

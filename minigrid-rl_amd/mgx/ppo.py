@@ -74,12 +74,23 @@ class PPOConfig:
     fused_update: bool = False          # with fused_train + fused_mission: loss, gradient clip and Adam through
                                         # mgx_ppo_loss / mgx_adam_step on one flat parameter arena, no autograd
                                         # (mgx/fused_update.py)
+    graph_collect: bool = False         # with fused_act, compact layout: a whole collect() -- act, step, truncation
+                                        # bootstrap (mgx_policy_bootstrap), episode statistics, last values, GAE --
+                                        # is one captured graph per ring block, replayed with no host decision
 
     def __post_init__(self):
+        if self.graph_collect and not (self.fused_act and self.layout == "compact"):
+            raise ValueError("graph_collect needs fused_act and layout='compact'")
         if self.fused_mission and not (self.fused_train or self.fused_act):
             raise ValueError("fused_mission needs fused_train or fused_act")
         if self.fused_update and not (self.fused_train and self.fused_mission and self.layout == "compact"):
             raise ValueError("fused_update needs fused_train, fused_mission and layout='compact'")
+
+
+def graph_refill_every(horizon):
+    """The engine's refill epoch for a graph-captured collect of `horizon` steps: the largest divisor of the
+    horizon that is <= 64 (the engine's default epoch), so that every rollout holds whole epochs."""
+    return max(d for d in range(1, 65) if horizon % d == 0)
 
 
 def linear_schedule(initial_value, final_value):
@@ -259,6 +270,20 @@ class CompactRolloutCollector:
         if getattr(cfg, "fused_act", False):
             from .fused_policy import FusedActor
             self.fused = FusedActor(policy, engine, seed=cfg.seed, fused_mission=getattr(cfg, "fused_mission", False))
+        self.graphs = None                 # cfg.graph_collect: one captured collect per ring block, made on first use
+        if getattr(cfg, "graph_collect", False):
+            if self.fused is None:
+                raise ValueError("graph_collect needs fused_act")
+            if engine.ring_depth > 0 and cfg.horizon % engine.refill_every:
+                raise ValueError("graph_collect: the horizon (%d) must be a multiple of the engine's refill epoch "
+                                 "(refill_every = %d)" % (cfg.horizon, engine.refill_every))
+            self.graphs = {}
+            T, N = cfg.horizon, engine.n
+            f32 = dict(dtype=torch.float32, device=engine.device)
+            self._ep_r, self._ep_l = torch.zeros((T, N), **f32), torch.zeros((T, N), **f32)
+            self._last_values = torch.zeros(N, **f32)
+            self._nan = torch.full((), math.nan, **f32)     # torch.where(..., out=) takes no scalar
+            self._stream = torch.cuda.Stream(engine.device)
         n, k, dev = engine.n, engine.n_stack, engine.device
         self._obs = dict(image=torch.empty((n, 3 * k, 7, 7), dtype=torch.float32, device=dev),
                          direction=torch.empty((n, 4 * k), dtype=torch.float32, device=dev),
@@ -273,6 +298,10 @@ class CompactRolloutCollector:
     def collect(self, callback=None):
         e, pol, cfg, ro = self.engine, self.policy, self.cfg, self.rollout
         buf, fused = ro.buf, self.fused
+        if self.graphs is not None:
+            if callback is not None:
+                raise ValueError("graph_collect: a callback needs a host decision every step")
+            return self._collect_graph()
         if fused is not None:
             fused.sync()                   # the optimiser phase since the last rollout changed the weights
         if self._n_rollouts:
@@ -316,6 +345,60 @@ class CompactRolloutCollector:
         r, l = torch.stack(ep_r), torch.stack(ep_l)
         m = ~torch.isnan(r)
         self.ep_returns, self.ep_lens = r[m], l[m]
+        return ro
+
+
+    def _capture(self):
+        """Capture the collect of the current ring block: every launch of a rollout, none executed.  The Python
+        bookkeeping the captured calls do (engine.calls) is redone by the caller on every replay."""
+        e, cfg, ro, fused = self.engine, self.cfg, self.rollout, self.fused
+        buf = ro.buf
+        from .engine import _stats_scratch
+        e.join()
+        torch.cuda.synchronize(e.device)
+        fused.index_table(buf)
+        calls = e.calls
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(self._stream):
+            _stats_scratch(ro.adv_stats)   # the GAE scratch of the capture stream: allocated outside the graph
+            g.capture_begin()
+            ro.adv_stats.zero_()
+            for t in range(cfg.horizon):
+                actions, _, _ = fused.act(buf, t, out=(ro.actions[t], ro.values[t], ro.log_probs[t]))
+                buf.step(t, actions)
+                fused.bootstrap(buf, t, cfg.gamma)
+                d = buf.dones[t].bool()
+                torch.where(d, e.ep_return, self._nan, out=self._ep_r[t])
+                torch.where(d, e.ep_len.float(), self._nan, out=self._ep_l[t])
+            fused.values(buf, cfg.horizon, out=self._last_values)
+            ro.compute_returns_and_advantage(self._last_values, cfg.gamma, cfg.gae_lambda)
+            e.join()                       # the graph is self-contained: the last epoch's refill ends inside it
+            g.capture_end()
+        torch.cuda.synchronize(e.device)
+        e.calls = calls
+        return g
+
+    def _collect_graph(self):
+        """collect() with cfg.graph_collect: sync the weights in place, replay the block's graph, read the episode
+        statistics once."""
+        e, cfg, ro, fused = self.engine, self.cfg, self.rollout, self.fused
+        buf = ro.buf
+        if e.ring_depth > 0 and e.calls % e.refill_every:
+            raise ValueError("graph_collect: a rollout must start on a refill-epoch boundary (engine.calls = %d, "
+                             "refill_every = %d)" % (e.calls, e.refill_every))
+        fused.sync()                       # eager and in place: the graphs read the new weights
+        if self._n_rollouts:
+            buf.carry_over()               # the block advance (ring: no device work)
+        self._n_rollouts += 1
+        self.policy.train(False)
+        g = self.graphs.get(buf.block)
+        if g is None:
+            g = self.graphs[buf.block] = self._capture()
+        g.replay()
+        e.calls += cfg.horizon             # what the replayed buf.step calls would have counted
+        self.num_timesteps += cfg.horizon * e.n
+        m = ~torch.isnan(self._ep_r)
+        self.ep_returns, self.ep_lens = self._ep_r[m], self._ep_l[m]
         return ro
 
 
@@ -465,9 +548,10 @@ def learn(cfg, total_timesteps, device="cuda", group=None, rank=0, log=None, cal
     from .policy import ActorCriticPolicy
     init = init or {}
     torch.manual_seed(cfg.seed + rank + init.get("seed_offset", 0))
+    graph = dict(refill_every=graph_refill_every(cfg.horizon)) if getattr(cfg, "graph_collect", False) else {}
     eng = MgxEngine(n_envs=cfg.n_envs, seed=cfg.seed + init.get("seed_offset", 0), env_index_offset=rank * cfg.n_envs,
                     n_stack=cfg.n_frames_stack, terminal_mode="truncated", mission_dtype=torch.uint8,
-                    device=device, reward64=True, **cfg.env)
+                    device=device, reward64=True, **graph, **cfg.env)
     pol = ActorCriticPolicy(n_stack=cfg.n_frames_stack, optim_eps=cfg.optim_eps, lr=cfg.initial_learning_rate,
                             mission_cache=cfg.mission_cache).to(eng.device)
     if "policy" in init:
