@@ -423,6 +423,21 @@ mgx_status mgx_mission_backward(const uint8_t *tokens_dev, int64_t n_rows, int s
                                 const float *g_features_dev, float *workspace_dev, int64_t workspace_words,
                                 const mgx_mission_grads *g, void *stream);
 
+/* The same two calls reading and writing rows of a table in place (added within ABI 9): row r's feature goes
+ * to table_dev[rows_dev[r]][128] instead of features_dev[r], and row r's cotangent is read from
+ * g_table_dev[rows_dev[r]][128] -- what forward + index_copy_ and index_select + backward do, bit for bit,
+ * without the two torch launches.  table_dev / g_table_dev f32 [table_rows][128]; rows_dev i64 [n_rows] on the
+ * device.  Table rows that rows_dev does not name are neither read nor written.  An index outside
+ * [0, table_rows) is the caller's error (the host cannot see it).  Everything else as above; additionally
+ * MGX_ERR_INVALID for a null rows_dev and table_rows < 1. */
+mgx_status mgx_mission_forward_rows(const uint8_t *tokens_dev, int64_t n_rows, int seq_len,
+                                    const mgx_mission_params *p, float *table_dev, const int64_t *rows_dev,
+                                    int64_t table_rows, float *workspace_dev, int64_t workspace_words, void *stream);
+mgx_status mgx_mission_backward_rows(const uint8_t *tokens_dev, int64_t n_rows, int seq_len,
+                                     const mgx_mission_params *p, const float *g_table_dev, const int64_t *rows_dev,
+                                     int64_t table_rows, float *workspace_dev, int64_t workspace_words,
+                                     const mgx_mission_grads *g, void *stream);
+
 /* ---- PPO loss: statistics and cotangents (added within ABI 9) ----------------------------------------
  * Replaces the loss block of SB3's PPO.train (stable_baselines3/ppo/ppo.py; mgx/ppo.py Trainer.train) and its
  * autograd graph down to the network outputs: from the logits and values mgx_policy_act (mode 0) wrote and
@@ -489,8 +504,9 @@ mgx_status mgx_ppo_loss(int64_t n_samples, const mgx_ppo_loss_args *a, void *str
  *    exp_avg <- exp_avg + (1 - beta1) (grad - exp_avg),  exp_avg_sq <- beta2 exp_avg_sq + (1 - beta2) grad^2
  *    param <- param - lr / (1 - beta1^step) * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^step) + eps)
  * The bias corrections are formed on the host in double from `step`, as torch forms them.  lr and the
- * corrections are therefore by-value arguments: a captured graph bakes them in, so a schedule or the next
- * step needs a new capture (or updated kernel-node parameters).  Non-finite gradients propagate exactly as in
+ * corrections are therefore by-value arguments of mgx_adam_step: a captured graph bakes them in.
+ * mgx_adam_step_sched (below) reads them from a device table instead, so one captured graph serves every step
+ * of a schedule; betas, eps, max_grad_norm and grad_scale stay by value in both (constant over a run).  Non-finite gradients propagate exactly as in
  * torch (a NaN norm makes every gradient NaN); there is no special case.
  *
  * Summation order.  The norm is summed as mgx_ppo_loss sums: ceil(n_words / 1024) workgroups, at most 256,
@@ -515,6 +531,32 @@ typedef struct mgx_adam_args {
 mgx_status mgx_adam_step(float *param_dev, float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev,
                          int64_t n_words, const mgx_adam_args *a, float *total_norm_dev, float *scratch_dev,
                          int64_t scratch_words, void *stream);
+
+/* Device-scheduled Adam (added within ABI 9): the two scalars of a step that change from step to step. */
+typedef struct mgx_adam_sched {
+    float step_size;                /* (float)(lr / (1 - beta1^step)) */
+    float bc2_sqrt;                 /* (float)sqrt(1 - beta2^step) */
+} mgx_adam_sched;
+
+/* Host only, no HIP call: out_host[i] = the entry of step first_step + i at learning rate lr[i], i < n, by the
+ * very function mgx_adam_step forms them with (double precision, then cast).  a->lr and a->step are ignored.
+ * MGX_ERR_INVALID for: a null pointer, first_step < 1, n < 1, a beta outside [0, 1), eps < 0. */
+mgx_status mgx_adam_schedule(const mgx_adam_args *a, const double *lr, int64_t first_step, int32_t n,
+                             mgx_adam_sched *out_host);
+
+/* mgx_adam_step with step_size and bc2_sqrt read from table_dev (mgx_adam_sched [table_len], on the device)
+ * at a device-side cursor; a->lr and a->step are ignored, the rest of `a` is by value.  cursor_dev int32 [2] =
+ * {next entry, overrun count}: thread 0 of the norm launch's first workgroup reads c = cursor[0] and writes
+ * c + 1 (the only writer); the step launch of the same call uses entry cursor[0] - 1 (stream order).  With
+ * that entry >= table_len the call updates nothing (total_norm_dev included) and adds 1 to cursor[1].  Plain
+ * stores, no atomics.  The same kernels, arithmetic, summation order and grid as mgx_adam_step: every output is
+ * bitwise what mgx_adam_step writes for the entry's (lr, step).  Calls that share a cursor must be on one
+ * stream.  Validation as mgx_adam_step (step excepted), and MGX_ERR_INVALID for a null table_dev or
+ * cursor_dev and table_len < 1, before any HIP call. */
+mgx_status mgx_adam_step_sched(float *param_dev, float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev,
+                               int64_t n_words, const mgx_adam_args *a, const mgx_adam_sched *table_dev,
+                               int32_t table_len, int32_t *cursor_dev, float *total_norm_dev, float *scratch_dev,
+                               int64_t scratch_words, void *stream);
 
 /* Makes `stream` wait for the in-flight refill, if any (no host sync). */
 mgx_status mgx_join(mgx_handle *h, void *stream);

@@ -3960,10 +3960,10 @@ static bool mission_params_ok(const mgx_mission_params *p) {
     return p && p->embedding_dev && p->w_ih_dev && p->w_hh_dev && p->b_ih_dev && p->b_hh_dev;
 }
 
-mgx_status mgx_mission_forward(const uint8_t *tokens_dev, int64_t n_rows, int seq_len, const mgx_mission_params *p,
-                               float *features_dev, float *workspace_dev, int64_t workspace_words, void *stream) {
-    if (!tokens_dev || !features_dev || !mission_params_ok(p))
-        return fail(MGX_ERR_INVALID, "mgx_mission_forward: null pointer");
+// mgx_mission_forward (rows_dev null: features_dev is [n_rows][128]) and mgx_mission_forward_rows (a table)
+static mgx_status mission_forward(const uint8_t *tokens_dev, int64_t n_rows, int seq_len, const mgx_mission_params *p,
+                                  float *features_dev, const int64_t *rows_dev, float *workspace_dev,
+                                  int64_t workspace_words, void *stream) {
     const int64_t need = mgx_mission_workspace_words(n_rows, seq_len);
     if (need < 0) return fail(MGX_ERR_INVALID, "mgx_mission_forward: n_rows must be in 1..2048, seq_len in 1..256");
     if (workspace_dev && workspace_words < need)
@@ -3971,19 +3971,36 @@ mgx_status mgx_mission_forward(const uint8_t *tokens_dev, int64_t n_rows, int se
     MissionArgs a;
     a.tokens = tokens_dev; a.n_rows = n_rows; a.T = seq_len;
     a.emb = p->embedding_dev; a.w_ih = p->w_ih_dev; a.w_hh = p->w_hh_dev; a.b_ih = p->b_ih_dev; a.b_hh = p->b_hh_dev;
-    a.feat = features_dev; a.g_feat = nullptr; a.ws = workspace_dev;
+    a.feat = features_dev; a.g_feat = nullptr; a.ws = workspace_dev; a.rows = rows_dev;
     const unsigned nblk = (unsigned)((n_rows + MS_ROWS - 1) / MS_ROWS);
-    hipLaunchKernelGGL(mgx_mission_forward_kernel, dim3(nblk), dim3(MS_THREADS), 0, (hipStream_t)stream, a);
+    if (rows_dev)
+        hipLaunchKernelGGL(mgx_mission_forward_kernel<true>, dim3(nblk), dim3(MS_THREADS), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(mgx_mission_forward_kernel<false>, dim3(nblk), dim3(MS_THREADS), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return MGX_OK;
 }
 
-mgx_status mgx_mission_backward(const uint8_t *tokens_dev, int64_t n_rows, int seq_len, const mgx_mission_params *p,
-                                const float *g_features_dev, float *workspace_dev, int64_t workspace_words,
-                                const mgx_mission_grads *g, void *stream) {
-    if (!tokens_dev || !g_features_dev || !workspace_dev || !mission_params_ok(p) || !g || !g->embedding_dev ||
-        !g->w_ih_dev || !g->w_hh_dev || !g->b_ih_dev || !g->b_hh_dev)
-        return fail(MGX_ERR_INVALID, "mgx_mission_backward: null pointer");
+mgx_status mgx_mission_forward(const uint8_t *tokens_dev, int64_t n_rows, int seq_len, const mgx_mission_params *p,
+                               float *features_dev, float *workspace_dev, int64_t workspace_words, void *stream) {
+    if (!tokens_dev || !features_dev || !mission_params_ok(p))
+        return fail(MGX_ERR_INVALID, "mgx_mission_forward: null pointer");
+    return mission_forward(tokens_dev, n_rows, seq_len, p, features_dev, nullptr, workspace_dev, workspace_words, stream);
+}
+
+mgx_status mgx_mission_forward_rows(const uint8_t *tokens_dev, int64_t n_rows, int seq_len,
+                                    const mgx_mission_params *p, float *table_dev, const int64_t *rows_dev,
+                                    int64_t table_rows, float *workspace_dev, int64_t workspace_words, void *stream) {
+    if (!tokens_dev || !table_dev || !rows_dev || !mission_params_ok(p))
+        return fail(MGX_ERR_INVALID, "mgx_mission_forward_rows: null pointer");
+    if (table_rows < 1) return fail(MGX_ERR_INVALID, "mgx_mission_forward_rows: table_rows must be positive");
+    return mission_forward(tokens_dev, n_rows, seq_len, p, table_dev, rows_dev, workspace_dev, workspace_words, stream);
+}
+
+// mgx_mission_backward (rows_dev null: g_features_dev is [n_rows][128]) and mgx_mission_backward_rows (a table)
+static mgx_status mission_backward(const uint8_t *tokens_dev, int64_t n_rows, int seq_len, const mgx_mission_params *p,
+                                   const float *g_features_dev, const int64_t *rows_dev, float *workspace_dev,
+                                   int64_t workspace_words, const mgx_mission_grads *g, void *stream) {
     const int64_t need = mgx_mission_workspace_words(n_rows, seq_len);
     if (need < 0) return fail(MGX_ERR_INVALID, "mgx_mission_backward: n_rows must be in 1..2048, seq_len in 1..256");
     if (workspace_words < need)
@@ -3993,9 +4010,12 @@ mgx_status mgx_mission_backward(const uint8_t *tokens_dev, int64_t n_rows, int s
     MissionArgs a;
     a.tokens = tokens_dev; a.n_rows = n_rows; a.T = seq_len;
     a.emb = p->embedding_dev; a.w_ih = p->w_ih_dev; a.w_hh = p->w_hh_dev; a.b_ih = p->b_ih_dev; a.b_hh = p->b_hh_dev;
-    a.feat = nullptr; a.g_feat = g_features_dev; a.ws = workspace_dev;
+    a.feat = nullptr; a.g_feat = g_features_dev; a.ws = workspace_dev; a.rows = rows_dev;
     const unsigned nblk = (unsigned)((n_rows + MS_ROWS - 1) / MS_ROWS);
-    hipLaunchKernelGGL(mgx_mission_bptt_kernel, dim3(nblk), dim3(MS_THREADS), 0, (hipStream_t)stream, a);
+    if (rows_dev)
+        hipLaunchKernelGGL(mgx_mission_bptt_kernel<true>, dim3(nblk), dim3(MS_THREADS), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(mgx_mission_bptt_kernel<false>, dim3(nblk), dim3(MS_THREADS), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     MissionWArgs w;
     w.tokens = tokens_dev; w.ws = workspace_dev; w.K = (int)pairs; w.T = seq_len;
@@ -4014,6 +4034,30 @@ mgx_status mgx_mission_backward(const uint8_t *tokens_dev, int64_t n_rows, int s
                        g->w_ih_dev, g->b_ih_dev, g->b_hh_dev);
     HIP_TRY(hipGetLastError());
     return MGX_OK;
+}
+
+static bool mission_grads_ok(const mgx_mission_grads *g) {
+    return g && g->embedding_dev && g->w_ih_dev && g->w_hh_dev && g->b_ih_dev && g->b_hh_dev;
+}
+
+mgx_status mgx_mission_backward(const uint8_t *tokens_dev, int64_t n_rows, int seq_len, const mgx_mission_params *p,
+                                const float *g_features_dev, float *workspace_dev, int64_t workspace_words,
+                                const mgx_mission_grads *g, void *stream) {
+    if (!tokens_dev || !g_features_dev || !workspace_dev || !mission_params_ok(p) || !mission_grads_ok(g))
+        return fail(MGX_ERR_INVALID, "mgx_mission_backward: null pointer");
+    return mission_backward(tokens_dev, n_rows, seq_len, p, g_features_dev, nullptr, workspace_dev, workspace_words, g,
+                            stream);
+}
+
+mgx_status mgx_mission_backward_rows(const uint8_t *tokens_dev, int64_t n_rows, int seq_len,
+                                     const mgx_mission_params *p, const float *g_table_dev, const int64_t *rows_dev,
+                                     int64_t table_rows, float *workspace_dev, int64_t workspace_words,
+                                     const mgx_mission_grads *g, void *stream) {
+    if (!tokens_dev || !g_table_dev || !rows_dev || !workspace_dev || !mission_params_ok(p) || !mission_grads_ok(g))
+        return fail(MGX_ERR_INVALID, "mgx_mission_backward_rows: null pointer");
+    if (table_rows < 1) return fail(MGX_ERR_INVALID, "mgx_mission_backward_rows: table_rows must be positive");
+    return mission_backward(tokens_dev, n_rows, seq_len, p, g_table_dev, rows_dev, workspace_dev, workspace_words, g,
+                            stream);
 }
 
 // ---- PPO loss and clip + Adam (mgx_update.h): no engine handle
@@ -4069,19 +4113,45 @@ mgx_status mgx_ppo_loss(int64_t n_samples, const mgx_ppo_loss_args *p, void *str
     return MGX_OK;
 }
 
-mgx_status mgx_adam_step(float *param_dev, float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev,
-                         int64_t n_words, const mgx_adam_args *p, float *total_norm_dev, float *scratch_dev,
-                         int64_t scratch_words, void *stream) {
-    if (!param_dev || !grad_dev || !exp_avg_dev || !exp_avg_sq_dev || !p || !scratch_dev)
-        return fail(MGX_ERR_INVALID, "mgx_adam_step: null pointer");
-    if (n_words <= 0) return fail(MGX_ERR_INVALID, "mgx_adam_step: n_words must be positive");
-    if (p->step < 1) return fail(MGX_ERR_INVALID, "mgx_adam_step: step counts from 1");
-    if (!(p->beta1 >= 0.0 && p->beta1 < 1.0) || !(p->beta2 >= 0.0 && p->beta2 < 1.0))
-        return fail(MGX_ERR_INVALID, "mgx_adam_step: betas must be in [0, 1)");
-    if (!(p->eps >= 0.0)) return fail(MGX_ERR_INVALID, "mgx_adam_step: eps must not be negative");
+// torch.optim.Adam (_single_tensor_adam): the corrections in double from the step count, cast where they meet fp32.
+// The one place the two per-step scalars are formed: mgx_adam_step and mgx_adam_schedule both call it.
+static mgx_adam_sched adam_sched_entry(const mgx_adam_args *p, double lr, int64_t step) {
+    const double bc1 = 1.0 - std::pow(p->beta1, (double)step), bc2 = 1.0 - std::pow(p->beta2, (double)step);
+    mgx_adam_sched e;
+    e.step_size = (float)(lr / bc1);
+    e.bc2_sqrt = (float)std::sqrt(bc2);
+    return e;
+}
+
+// what: the entry point's name; nullptr when the constants are fine
+static const char *adam_consts_bad(const mgx_adam_args *p) {
+    if (!(p->beta1 >= 0.0 && p->beta1 < 1.0) || !(p->beta2 >= 0.0 && p->beta2 < 1.0)) return "betas must be in [0, 1)";
+    if (!(p->eps >= 0.0)) return "eps must not be negative";
+    return nullptr;
+}
+
+mgx_status mgx_adam_schedule(const mgx_adam_args *p, const double *lr, int64_t first_step, int32_t n,
+                             mgx_adam_sched *out_host) {
+    if (!p || !lr || !out_host) return fail(MGX_ERR_INVALID, "mgx_adam_schedule: null pointer");
+    if (first_step < 1) return fail(MGX_ERR_INVALID, "mgx_adam_schedule: step counts from 1");
+    if (n < 1) return fail(MGX_ERR_INVALID, "mgx_adam_schedule: n must be positive");
+    if (const char *bad = adam_consts_bad(p)) return fail(MGX_ERR_INVALID, std::string("mgx_adam_schedule: ") + bad);
+    for (int32_t i = 0; i < n; i++) out_host[i] = adam_sched_entry(p, lr[i], first_step + i);
+    return MGX_OK;
+}
+
+// mgx_adam_step (table_dev null: lr and step from p) and mgx_adam_step_sched (p->lr and p->step ignored)
+static mgx_status adam_step(const char *what, float *param_dev, float *grad_dev, float *exp_avg_dev,
+                            float *exp_avg_sq_dev, int64_t n_words, const mgx_adam_args *p,
+                            const mgx_adam_sched *table_dev, int32_t table_len, int32_t *cursor_dev,
+                            float *total_norm_dev, float *scratch_dev, int64_t scratch_words, void *stream) {
+    const std::string w = std::string(what) + ": ";
+    if (n_words <= 0) return fail(MGX_ERR_INVALID, w + "n_words must be positive");
+    if (!table_dev && p->step < 1) return fail(MGX_ERR_INVALID, w + "step counts from 1");
+    if (const char *bad = adam_consts_bad(p)) return fail(MGX_ERR_INVALID, w + bad);
     if (scratch_words < mgx_adam_scratch_words(n_words))
-        return fail(MGX_ERR_INVALID, "mgx_adam_step: scratch_words below mgx_adam_scratch_words");
-    if ((uintptr_t)scratch_dev & 7) return fail(MGX_ERR_INVALID, "mgx_adam_step: scratch_dev must be 8-byte aligned");
+        return fail(MGX_ERR_INVALID, w + "scratch_words below mgx_adam_scratch_words");
+    if ((uintptr_t)scratch_dev & 7) return fail(MGX_ERR_INVALID, w + "scratch_dev must be 8-byte aligned");
     AdamArgs a;
     a.param = param_dev; a.grad = grad_dev; a.exp_avg = exp_avg_dev; a.exp_avg_sq = exp_avg_sq_dev;
     a.norm_out = total_norm_dev; a.part = (double *)scratch_dev;
@@ -4089,15 +4159,44 @@ mgx_status mgx_adam_step(float *param_dev, float *grad_dev, float *exp_avg_dev, 
     a.groups = update_groups(n_words, UP_ADAM_PER_GROUP);
     a.grad_scale = (float)p->grad_scale;
     a.max_norm = p->max_grad_norm > 0.0 ? (float)p->max_grad_norm : 0.f;
-    // torch.optim.Adam (_single_tensor_adam): the corrections in double from the step count, cast where they meet fp32
-    const double bc1 = 1.0 - std::pow(p->beta1, (double)p->step), bc2 = 1.0 - std::pow(p->beta2, (double)p->step);
     a.w1 = (float)(1.0 - p->beta1); a.beta2 = (float)p->beta2; a.w2 = (float)(1.0 - p->beta2);
-    a.step_size = (float)(p->lr / bc1); a.bc2_sqrt = (float)std::sqrt(bc2); a.eps = (float)p->eps;
-    hipLaunchKernelGGL(mgx_adam_norm_kernel, dim3((unsigned)a.groups), dim3(UP_THREADS), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(mgx_adam_step_kernel, dim3((unsigned)a.groups), dim3(UP_THREADS), 0, (hipStream_t)stream, a);
+    a.eps = (float)p->eps;
+    a.sched = table_dev; a.sched_len = table_len; a.cursor = cursor_dev;
+    a.step_size = 0.f; a.bc2_sqrt = 1.f;
+    const dim3 grid((unsigned)a.groups), block(UP_THREADS);
+    if (table_dev) {
+        hipLaunchKernelGGL(mgx_adam_norm_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(mgx_adam_step_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
+    } else {
+        const mgx_adam_sched e = adam_sched_entry(p, p->lr, p->step);
+        a.step_size = e.step_size; a.bc2_sqrt = e.bc2_sqrt;
+        hipLaunchKernelGGL(mgx_adam_norm_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(mgx_adam_step_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
+    }
     HIP_TRY(hipGetLastError());
     return MGX_OK;
+}
+
+mgx_status mgx_adam_step(float *param_dev, float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev,
+                         int64_t n_words, const mgx_adam_args *p, float *total_norm_dev, float *scratch_dev,
+                         int64_t scratch_words, void *stream) {
+    if (!param_dev || !grad_dev || !exp_avg_dev || !exp_avg_sq_dev || !p || !scratch_dev)
+        return fail(MGX_ERR_INVALID, "mgx_adam_step: null pointer");
+    return adam_step("mgx_adam_step", param_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n_words, p, nullptr, 0, nullptr,
+                     total_norm_dev, scratch_dev, scratch_words, stream);
+}
+
+mgx_status mgx_adam_step_sched(float *param_dev, float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev,
+                               int64_t n_words, const mgx_adam_args *p, const mgx_adam_sched *table_dev,
+                               int32_t table_len, int32_t *cursor_dev, float *total_norm_dev, float *scratch_dev,
+                               int64_t scratch_words, void *stream) {
+    if (!param_dev || !grad_dev || !exp_avg_dev || !exp_avg_sq_dev || !p || !scratch_dev || !table_dev || !cursor_dev)
+        return fail(MGX_ERR_INVALID, "mgx_adam_step_sched: null pointer");
+    if (table_len < 1) return fail(MGX_ERR_INVALID, "mgx_adam_step_sched: table_len must be positive");
+    return adam_step("mgx_adam_step_sched", param_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n_words, p, table_dev,
+                     table_len, cursor_dev, total_norm_dev, scratch_dev, scratch_words, stream);
 }
 
 mgx_status mgx_gae(const float *rewards_dev, const float *values_dev, const float *episode_starts_dev,

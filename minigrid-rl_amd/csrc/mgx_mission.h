@@ -46,6 +46,7 @@ struct MissionArgs {
     float *feat;                            // forward: [n_rows][128]
     const float *g_feat;                    // backward: [n_rows][128]
     float *ws;                              // step records [n_rows][T][MS_REC]; forward: may be null
+    const int64_t *rows;                    // ROWS: row r's feature / cotangent is row rows[r] of feat / g_feat
 };
 
 // 0 and 1 for large |x| (expf gives inf or 0), never NaN
@@ -79,6 +80,8 @@ __device__ __forceinline__ void ms_matvec(const float (&w)[MS_H], float (&acc)[M
         acc[i] = ((p[i][0] + p[i][1]) + (p[i][2] + p[i][3])) + ((p[i][4] + p[i][5]) + (p[i][6] + p[i][7]));
 }
 
+// ROWS (mgx_mission_forward_rows): the one store below goes to row a.rows[myrow] of a table, nothing else differs.
+template <bool ROWS>
 __global__ __launch_bounds__(MS_THREADS) void mgx_mission_forward_kernel(MissionArgs a) {
     __shared__ float sG[MS_V * MS_G];                                 // G[tok][j]
     __shared__ __align__(16) float sH[2][MS_ROWS][MS_H];
@@ -149,11 +152,13 @@ __global__ __launch_bounds__(MS_THREADS) void mgx_mission_forward_kernel(Mission
         cur ^= 1;
         __syncthreads();
     }
-    if (live) a.feat[myrow * MS_H + u] = sH[cur][ri][u];
+    if (live) a.feat[(ROWS ? a.rows[myrow] : myrow) * MS_H + u] = sH[cur][ri][u];
 }
 
 // Backward through time.  Record slots on return: h_t | da_r | da_z | da_n | da_n r  (a_* the gate pre-activations;
 // slots 1..3 are the input-side cotangents, 1, 2 and 4 the hidden-side ones).
+// ROWS (mgx_mission_backward_rows): the one load of the cotangent reads row a.rows[myrow] of a table.
+template <bool ROWS>
 __global__ __launch_bounds__(MS_THREADS) void mgx_mission_bptt_kernel(MissionArgs a) {
     __shared__ __align__(16) float sC[MS_ROWS][MS_G];                 // hidden-side cotangents of this step
     __shared__ float sP[MS_ROWS][3][MS_H];                            // the three partial products per (row, unit)
@@ -167,7 +172,7 @@ __global__ __launch_bounds__(MS_THREADS) void mgx_mission_bptt_kernel(MissionArg
 #pragma unroll
     for (int k = 0; k < MS_H; k++) wt[k] = a.w_hh[(size_t)(part * MS_H + k) * MS_H + u];
     float *rec = a.ws + (size_t)(live ? myrow : 0) * T * MS_REC + u;
-    float dh = live ? a.g_feat[myrow * MS_H + u] : 0.0f;
+    float dh = live ? a.g_feat[(ROWS ? a.rows[myrow] : myrow) * MS_H + u] : 0.0f;
     float r = 0.0f, z = 0.0f, n = 0.0f, q = 0.0f, hp = 0.0f;
     const auto load = [&](int t, float &r_, float &z_, float &n_, float &q_, float &hp_) {
         r_ = z_ = n_ = q_ = hp_ = 0.0f;

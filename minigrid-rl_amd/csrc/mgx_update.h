@@ -1,4 +1,5 @@
-// The PPO update's tail (include/mgx.h, added within ABI 9): mgx_ppo_loss and mgx_adam_step.  DESIGN.md §4.9.
+// The PPO update's tail (include/mgx.h, added within ABI 9): mgx_ppo_loss and mgx_adam_step, and
+// mgx_adam_step_sched, the same step with its per-step scalars read from a device table (§4.11).
 //
 // mgx_ppo_loss   PPO.train's loss block on the (logits, values) mgx_policy_act mode 0 wrote: the loss, its
 //                statistics and the cotangents mgx_policy_backward consumes, lane = sample, fp32 with expf / logf.
@@ -187,10 +188,20 @@ struct AdamArgs {
     int64_t n;
     int groups;
     float grad_scale, max_norm, w1, beta2, w2, step_size, bc2_sqrt, eps;
+    const mgx_adam_sched *sched;   // SCHED: [sched_len] (step_size, bc2_sqrt) per step; the two by-value ones unused
+    int32_t *cursor;               // SCHED: {next entry, overrun count}
+    int sched_len;
 };
 
+// SCHED (mgx_adam_step_sched): the two per-step scalars come from a device table, so a captured graph bakes in
+// nothing that changes from step to step.  Thread 0 of workgroup 0 of the norm launch is the cursor's only writer;
+// the step launch of the same call reads entry cursor[0] - 1 (stream order: the norm launch has finished, and the
+// next call's norm launch has not begun).  Arithmetic, summation order and grid are those of SCHED = false.
+
+template <bool SCHED>
 __global__ __launch_bounds__(UP_THREADS) void mgx_adam_norm_kernel(AdamArgs a) {
     __shared__ double lds[UP_THREADS];
+    if (SCHED && blockIdx.x == 0 && threadIdx.x == 0) a.cursor[0] = a.cursor[0] + 1;
     double v[1] = {0.0};
     for (int64_t i = (int64_t)blockIdx.x * UP_THREADS + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * UP_THREADS) {
         const double x = (double)(a.grad[i] * a.grad_scale);
@@ -200,9 +211,20 @@ __global__ __launch_bounds__(UP_THREADS) void mgx_adam_norm_kernel(AdamArgs a) {
     if (threadIdx.x == 0) a.part[blockIdx.x] = v[0];
 }
 
+template <bool SCHED>
 __global__ __launch_bounds__(UP_THREADS) void mgx_adam_step_kernel(AdamArgs a) {
     __shared__ double lds[UP_THREADS];
     const int t = threadIdx.x;
+    float step_size = a.step_size, bc2_sqrt = a.bc2_sqrt;
+    if (SCHED) {
+        const int e = a.cursor[0] - 1;
+        if (e < 0 || e >= a.sched_len) {                      // past the table: nothing is updated, the overrun counted
+            if (blockIdx.x == 0 && t == 0) a.cursor[1] = a.cursor[1] + 1;
+            return;                                           // uniform over the grid
+        }
+        step_size = a.sched[e].step_size;
+        bc2_sqrt = a.sched[e].bc2_sqrt;
+    }
     double v[1] = {t < a.groups ? a.part[t] : 0.0};
     up_block_sum<1>(v, lds);
     const float total = (float)sqrt(v[0]);
@@ -220,7 +242,7 @@ __global__ __launch_bounds__(UP_THREADS) void mgx_adam_step_kernel(AdamArgs a) {
         s = s * a.beta2 + a.w2 * (g * g);                     // mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
         a.exp_avg[i] = m;
         a.exp_avg_sq[i] = s;
-        const float denom = sqrtf(s) / a.bc2_sqrt + a.eps;
-        a.param[i] = a.param[i] - a.step_size * (m / denom);  // addcdiv_(exp_avg, denom, value=-step_size)
+        const float denom = sqrtf(s) / bc2_sqrt + a.eps;
+        a.param[i] = a.param[i] - step_size * (m / denom);  // addcdiv_(exp_avg, denom, value=-step_size)
     }
 }

@@ -30,7 +30,8 @@ EXPORTS = ("mgx_last_error", "mgx_abi_version", "mgx_create", "mgx_destroy", "mg
            "mgx_ring_levels", "mgx_random_actions", "mgx_set_random_policy", "mgx_policy_blob_words",
            "mgx_policy_act", "mgx_policy_bootstrap", "mgx_policy_grad_scratch_words", "mgx_policy_backward",
            "mgx_mission_workspace_words", "mgx_mission_forward", "mgx_mission_backward",
-           "mgx_ppo_loss_scratch_words", "mgx_ppo_loss", "mgx_adam_scratch_words", "mgx_adam_step")
+           "mgx_ppo_loss_scratch_words", "mgx_ppo_loss", "mgx_adam_scratch_words", "mgx_adam_step",
+           "mgx_mission_forward_rows", "mgx_mission_backward_rows", "mgx_adam_schedule", "mgx_adam_step_sched")
 CLOCK_CLASSES = 4   # == MGX_CLOCK_CLASSES (include/mgx.h)
 
 
@@ -146,6 +147,10 @@ class MgxAdamArgs(ctypes.Structure):
     ]
 
 
+class MgxAdamSched(ctypes.Structure):
+    _fields_ = [("step_size", ctypes.c_float), ("bc2_sqrt", ctypes.c_float)]
+
+
 class MgxError(RuntimeError):
     pass
 
@@ -201,12 +206,18 @@ def load():
     L.mgx_mission_forward.argtypes = [P, I64, I, ctypes.POINTER(MgxMissionParams), P, P, I64, P]
     L.mgx_mission_backward.argtypes = [P, I64, I, ctypes.POINTER(MgxMissionParams), P, P, I64,
                                        ctypes.POINTER(MgxMissionGrads), P]
+    L.mgx_mission_forward_rows.argtypes = [P, I64, I, ctypes.POINTER(MgxMissionParams), P, P, I64, P, I64, P]
+    L.mgx_mission_backward_rows.argtypes = [P, I64, I, ctypes.POINTER(MgxMissionParams), P, P, I64, P, I64,
+                                            ctypes.POINTER(MgxMissionGrads), P]
     L.mgx_ppo_loss_scratch_words.argtypes = [I64]
     L.mgx_ppo_loss_scratch_words.restype = I64
     L.mgx_ppo_loss.argtypes = [I64, ctypes.POINTER(MgxPpoLossArgs), P]
     L.mgx_adam_scratch_words.argtypes = [I64]
     L.mgx_adam_scratch_words.restype = I64
     L.mgx_adam_step.argtypes = [P, P, P, P, I64, ctypes.POINTER(MgxAdamArgs), P, P, I64, P]
+    L.mgx_adam_schedule.argtypes = [ctypes.POINTER(MgxAdamArgs), ctypes.POINTER(ctypes.c_double), I64, ctypes.c_int32,
+                                    ctypes.POINTER(MgxAdamSched)]
+    L.mgx_adam_step_sched.argtypes = [P, P, P, P, I64, ctypes.POINTER(MgxAdamArgs), P, ctypes.c_int32, P, P, P, I64, P]
     L.mgx_set_clock.argtypes = [P, P, I, ctypes.POINTER(I)]
     L.mgx_clock_words.argtypes = [P, I]
     L.mgx_clock_words.restype = I64

@@ -125,6 +125,48 @@ class FusedMissionEncoder:
                                                self._stream()), "mgx_mission_backward")
         return grads
 
+    def _check_table(self, table, rows, n):
+        if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != HIDDEN or \
+                not table.is_contiguous() or table.device != self.device:
+            raise ValueError("the table must be a contiguous f32 [table_rows, %d] tensor on %s" % (HIDDEN, self.device))
+        if rows.dtype != torch.int64 or not rows.is_contiguous() or rows.numel() != n or rows.device != self.device:
+            raise ValueError("rows must be a contiguous i64 tensor of %d elements on %s" % (n, self.device))
+
+    def forward_rows(self, tokens, params, table, rows, workspace=None):
+        """mgx_mission_forward_rows: row r's feature into table[rows[r]] (table f32 [table_rows, 128], rows i64
+        [n_rows]) -- forward_raw + table.index_copy_(0, rows, .) bit for bit, in one launch.  Indices outside the
+        table are the caller's error."""
+        n, t = self._check_tokens(tokens)
+        self._check_table(table, rows, n)
+        self._fill(self._p, params)
+        P = ctypes.c_void_p
+        _lib.check(self.L.mgx_mission_forward_rows(
+            P(tokens.data_ptr()), n, t, ctypes.byref(self._p), P(table.data_ptr()), P(rows.data_ptr()),
+            table.shape[0], None if workspace is None else P(workspace.data_ptr()),
+            0 if workspace is None else workspace.numel(), self._stream()), "mgx_mission_forward_rows")
+        return table
+
+    def backward_rows(self, tokens, params, g_table, rows, workspace, out=None):
+        """mgx_mission_backward_rows: backward_raw on g_table.index_select(0, rows) bit for bit, without the
+        index_select (g_table f32 [table_rows, 128]); rows it does not name are not read."""
+        n, t = self._check_tokens(tokens)
+        self._check_table(g_table, rows, n)
+        if out is None:
+            grads = tuple(torch.empty_like(p) for p in params)
+        else:
+            grads = tuple(out)
+            if len(grads) != 5 or any(o.dtype != torch.float32 or not o.is_contiguous() or o.shape != p.shape or
+                                      o.device != p.device for o, p in zip(grads, params)):
+                raise ValueError("out must be five contiguous f32 tensors shaped as params")
+        self._fill(self._p, params)
+        self._fill(self._g, grads)
+        P = ctypes.c_void_p
+        _lib.check(self.L.mgx_mission_backward_rows(
+            P(tokens.data_ptr()), n, t, ctypes.byref(self._p), P(g_table.data_ptr()), P(rows.data_ptr()),
+            g_table.shape[0], P(workspace.data_ptr()), workspace.numel(), ctypes.byref(self._g), self._stream()),
+            "mgx_mission_backward_rows")
+        return grads
+
     def encode(self, tokens_u8):
         """f32 [n_rows, 128]: the extractor's output on u8 [n_rows, seq_len] token rows.  Under autograd the result
         is connected to the five parameters; without it the forward runs with no workspace."""

@@ -100,11 +100,19 @@ class FusedEvaluator:
         _, tensors = _params(self.policy)
         return differentiable_blob(tensors), mission_table_rows(self.policy, self._rows, self._stacks, self.mission)
 
-    def forward_raw(self, buf, index, blob, mission_feat):
-        """mgx_policy_act mode 0 -> (logits f32 [B, 7], values f32 [B])."""
+    def forward_raw(self, buf, index, blob, mission_feat, out=None):
+        """mgx_policy_act mode 0 -> (logits f32 [B, 7], values f32 [B]); out: that pair as contiguous f32 tensors to
+        write into (a captured graph's persistent buffers)."""
         e, n = self.engine, index.numel()
-        logits = torch.empty((n, N_ACTIONS), dtype=torch.float32, device=e.device)
-        values = torch.empty(n, dtype=torch.float32, device=e.device)
+        if out is None:
+            logits = torch.empty((n, N_ACTIONS), dtype=torch.float32, device=e.device)
+            values = torch.empty(n, dtype=torch.float32, device=e.device)
+        else:
+            logits, values = out
+            for t, numel in ((logits, n * N_ACTIONS), (values, n)):
+                if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel or t.device != e.device:
+                    raise ValueError("out must be contiguous f32 tensors of %d and %d elements on %s"
+                                     % (n * N_ACTIONS, n, e.device))
         p, o = self._pol, self._out
         p.blob_dev, p.mission_feat_dev, p.mode = blob.data_ptr(), mission_feat.data_ptr(), 0
         o.actions_dev = o.log_probs_dev = None

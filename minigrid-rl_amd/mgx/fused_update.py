@@ -10,6 +10,13 @@ ParamArena is the storage that makes this possible: the 25 parameter tensors bec
 (the 20 blob tensors first, unpadded, so arena.param[:blob_words] IS the kernels' weight blob -- no torch.cat), their
 .grad views of a second one, Adam's moments two more.  mgx_policy_backward and mgx_mission_backward write their
 gradients straight into the gradient buffer; mgx_adam_step clips and steps the whole buffer in two launches.
+
+Graph-captured update (PPOConfig.graph_train).  The step above is a fixed sequence of launches, but
+mgx_adam_step takes lr and the bias corrections by value, so a captured graph would bake them in.
+mgx_adam_step_sched reads them from a device table at a device-side cursor, and mgx_mission_forward_rows /
+mgx_mission_backward_rows address the mission table in place (no index_copy_ / index_select), so FusedUpdate captures
+one graph of a whole epoch -- every minibatch on fixed slices of persistent index / sel buffers -- and Trainer.train
+replays it once per epoch: per epoch the host draws the permutation, copies it in and launches one graph.
 """
 import ctypes
 
@@ -181,6 +188,47 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lr, step, betas=(0.9, 0.999), ep
                                _ptr(total_norm), _ptr(scratch), scratch.numel(), _stream(dev)), "mgx_adam_step")
 
 
+def adam_schedule(lrs, first_step, betas=(0.9, 0.999), eps=1e-8):
+    """mgx_adam_schedule -> f32 [n, 2] on the host: row i = (step_size, bc2_sqrt) of step first_step + i at learning
+    rate lrs[i], formed as mgx_adam_step forms them."""
+    L = _lib.load()
+    lrs = [float(x) for x in lrs]
+    n = len(lrs)
+    a = _lib.MgxAdamArgs(lr=0.0, beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps), step=0,
+                         max_grad_norm=0.0, grad_scale=1.0)
+    out = (_lib.MgxAdamSched * max(n, 1))()
+    _lib.check(L.mgx_adam_schedule(ctypes.byref(a), (ctypes.c_double * max(n, 1))(*lrs), int(first_step), n, out),
+               "mgx_adam_schedule")
+    return torch.tensor([[e.step_size, e.bc2_sqrt] for e in out[:n]], dtype=torch.float64).to(torch.float32)
+
+
+def adam_step_sched(param, grad, exp_avg, exp_avg_sq, table, cursor, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0,
+                    grad_scale=1.0, total_norm=None, scratch=None):
+    """mgx_adam_step_sched: adam_step whose (lr, step) come from the device: table f32 [len, 2] as adam_schedule
+    returns it, cursor i32 [2] = {next entry, overrun count}.  Past the table's end nothing is updated and cursor[1]
+    counts the call."""
+    L = _lib.load()
+    n = param.numel()
+    for t, what in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _f32(t, n, what)
+    dev = param.device
+    if table.dtype != torch.float32 or not table.is_contiguous() or table.dim() != 2 or table.shape[1] != 2 or \
+            table.device != dev:
+        raise ValueError("table must be a contiguous f32 [len, 2] tensor on %s" % (dev,))
+    if cursor.dtype != torch.int32 or not cursor.is_contiguous() or cursor.numel() != 2 or cursor.device != dev:
+        raise ValueError("cursor must be a contiguous i32 [2] tensor on %s" % (dev,))
+    if scratch is None:
+        scratch = torch.empty(max(int(L.mgx_adam_scratch_words(n)), 2), dtype=torch.float32, device=dev)
+    a = _lib.MgxAdamArgs(lr=0.0, beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps), step=0,
+                         max_grad_norm=float(max_grad_norm) if max_grad_norm else 0.0, grad_scale=float(grad_scale))
+    _lib.check(L.mgx_adam_step_sched(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), n, ctypes.byref(a),
+                                     _ptr(table), table.shape[0], _ptr(cursor), _ptr(total_norm), _ptr(scratch),
+                                     scratch.numel(), _stream(dev)), "mgx_adam_step_sched")
+
+
+MAX_GRAPHS = 8                         # captured epoch graphs kept per FusedUpdate; the oldest is evicted
+
+
 class FusedUpdate:
     """One PPO minibatch step of `policy` on samples of a CompactBuffer of `engine` without torch.autograd:
     mgx_mission_forward, mgx_policy_act (mode 0), mgx_ppo_loss, mgx_policy_backward, mgx_mission_backward,
@@ -205,6 +253,9 @@ class FusedUpdate:
                                          device=dev)
         self._loss_scratch = torch.empty(int(L.mgx_ppo_loss_scratch_words(1 << 30)), dtype=torch.float32, device=dev)
         self._batch = {}               # B -> (g_logits, g_values)
+        self._graphs = {}              # graph_train: cache key -> (graph, stacks, rows, workspace), oldest first
+        self._gbuf = None              # graph_train: the persistent buffers of one (T * N, minibatch sizes, epochs)
+        self._gstream = None
         a = self.arena
         self._blob, self._g_blob = a.param[:a.blob_words], a.grad[:a.blob_words]
         self._mission = tuple(a.views(a.param, slice(20, 25)))
@@ -255,3 +306,116 @@ class FusedUpdate:
         adam_step(a.param, a.grad, a.exp_avg, a.exp_avg_sq, lr, a.step, betas=pg["betas"], eps=pg["eps"],
                   max_grad_norm=cfg.max_grad_norm, grad_scale=scale, total_norm=self.total_norm,
                   scratch=self._adam_scratch)
+
+    # ---- graph_train: one captured graph per epoch
+    def _graph_buffers(self, n, sizes, n_epochs):
+        """The persistent buffers the captured graphs address, for n samples in minibatches of `sizes`."""
+        shape = (n, sizes, n_epochs)
+        if self._gbuf is not None and self._gbuf["shape"] == shape:
+            return self._gbuf
+        self._graphs.clear()           # they address the old buffers
+        dev, L, top = self.engine.device, self.engine.L, max(sizes)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self._gbuf = dict(
+            shape=shape,
+            index=torch.zeros(n, dtype=torch.int64, device=dev), sel=torch.zeros(n, dtype=torch.int64, device=dev),
+            stats=torch.zeros((len(sizes), 8), **f32), adv_stats=torch.zeros(2, **f32),
+            sched=torch.zeros((n_epochs * len(sizes), 2), **f32), cursor=torch.zeros(2, dtype=torch.int32, device=dev),
+            logits=torch.empty((top, N_ACTIONS), **f32), values=torch.empty(top, **f32),
+            scratch=torch.empty(int(L.mgx_policy_grad_scratch_words(self.ev.K, top, self.ev.max_groups)), **f32))
+        if self._gstream is None:
+            self._gstream = torch.cuda.Stream(dev)
+        return self._gbuf
+
+    def _graph_step(self, b, buf, s, m, i, rollout, cfg, adv_mode, stacks, rows, ws):
+        """FusedUpdate.step on the fixed slice [s, s + m) of the persistent index / sel, every launch on persistent
+        memory: mgx_mission_forward_rows, mgx_policy_act, mgx_ppo_loss, mgx_policy_backward,
+        mgx_mission_backward_rows, mgx_adam_step_sched."""
+        ev, a, enc = self.ev, self.arena, self.ev.mission
+        if m not in self._batch:
+            raise RuntimeError("FusedUpdate: no gradient buffers for a minibatch of %d" % m)
+        g_logits, g_values = self._batch[m]
+        index, sel = b["index"][s:s + m], b["sel"][s:s + m]
+        enc.forward_rows(stacks, self._mission, self.table, rows, ws)
+        ev.forward_raw(buf, index, self._blob, self.table, out=(b["logits"][:m], b["values"][:m]))
+        ppo_loss(b["logits"][:m], b["values"][:m], *rollout, cfg.clip_range, cfg.clip_range_vf, cfg.ent_coef,
+                 cfg.vf_coef, adv_mode=adv_mode, sel=sel, adv_stats=b["adv_stats"] if adv_mode == 2 else None,
+                 out=(g_logits, g_values, b["stats"][i]), scratch=self._loss_scratch)
+        ev.backward_raw(buf, index, self._blob, self.table, g_logits, g_values, scratch=b["scratch"],
+                        out=(self._g_blob, self.g_table))
+        enc.backward_rows(stacks, self._mission, self.g_table.view(-1, 128), rows, ws, out=self._g_mission)
+        pg = self.policy.optimizer.param_groups[0]
+        adam_step_sched(a.param, a.grad, a.exp_avg, a.exp_avg_sq, b["sched"], b["cursor"], betas=pg["betas"],
+                        eps=pg["eps"], max_grad_norm=cfg.max_grad_norm, total_norm=self.total_norm,
+                        scratch=self._adam_scratch)
+
+    def _capture_epoch(self, b, buf, rollout, cfg, adv_mode):
+        """Capture one epoch -- every minibatch's launches in order on one stream, none executed."""
+        ev, enc, dev = self.ev, self.ev.mission, self.engine.device
+        stacks, rows = ev._stacks, ev._rows
+        ws = torch.empty(int(enc.L.mgx_mission_workspace_words(stacks.shape[0], stacks.shape[1])),
+                         dtype=torch.float32, device=dev)          # the graph's own: enc's is reallocated as it grows
+        for m in set(b["shape"][1]):
+            if m not in self._batch:
+                self._batch[m] = (torch.empty((m, N_ACTIONS), dtype=torch.float32, device=dev),
+                                  torch.empty(m, dtype=torch.float32, device=dev))
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(self._gstream):
+            g.capture_begin()
+            try:
+                s = 0
+                for i, m in enumerate(b["shape"][1]):
+                    self._graph_step(b, buf, s, m, i, rollout, cfg, adv_mode if m > 1 else 0, stacks, rows, ws)
+                    s += m
+            finally:
+                g.capture_end()
+        torch.cuda.synchronize(dev)
+        return g, stacks, rows, ws
+
+    def graph_begin(self, buf, rollout, cfg, lr, n_samples, adv_mode=1, adv_stats=None):
+        """After prepare(): the schedule of this train() call's n_epochs * n_minibatches steps at `lr`, from
+        arena.step + 1, and a zeroed cursor, to the device; returns the epoch graph of this call's by-value
+        arguments, captured now if the cache does not hold it."""
+        sizes = tuple(min(cfg.batch_size, n_samples - s) for s in range(0, n_samples, cfg.batch_size))
+        b = self._graph_buffers(n_samples, sizes, cfg.n_epochs)
+        pg = self.policy.optimizer.param_groups[0]
+        steps = cfg.n_epochs * len(sizes)
+        b["sched"].copy_(adam_schedule([lr] * steps, self.arena.step + 1, betas=pg["betas"], eps=pg["eps"]))
+        b["cursor"].zero_()
+        if adv_mode == 2:
+            b["adv_stats"].copy_(adv_stats)
+        self.ev.mission._ticket += 1   # a pending autograd encode() of this encoder loses the workspace
+        # everything the launches take by value: sizes and scalars, and the addresses that are not this object's own
+        # (sample_addr passes the buffer's base addresses, N and R: nothing of the ring block -- that is in `index`)
+        key = (tuple(self.ev._rows.tolist()), sizes, adv_mode, float(cfg.clip_range), float(cfg.clip_range_vf),
+               float(cfg.ent_coef), float(cfg.vf_coef), float(cfg.max_grad_norm), tuple(pg["betas"]), float(pg["eps"]),
+               id(buf), buf.rows.data_ptr(), buf.mids.data_ptr(), buf.starts.data_ptr(), buf.N, buf.R, buf.ring,
+               tuple(t.data_ptr() for t in rollout))
+        hit = self._graphs.get(key)
+        if hit is None:
+            while len(self._graphs) >= MAX_GRAPHS:
+                del self._graphs[next(iter(self._graphs))]
+            hit = self._graphs[key] = self._capture_epoch(b, buf, rollout, cfg, adv_mode)
+        return hit[0]
+
+    def graph_epoch(self, graph, index, sel):
+        """One epoch: the permutation's index / sel into the persistent buffers, one replay -> stats f32 [n_mb, 8]."""
+        b = self._gbuf
+        b["index"].copy_(index)
+        b["sel"].copy_(sel)
+        graph.replay()
+        return b["stats"].clone()
+
+    def graph_end(self, rows):
+        """After the last epoch: the step count, the optimizer state, and the one host read -> the mean statistics
+        row.  MgxError if the device ran past the schedule or did not take every entry."""
+        b = self._gbuf
+        steps = b["sched"].shape[0]
+        self.arena.step += steps
+        self.arena.export_state()
+        st = torch.cat([torch.cat(rows).mean(0), b["cursor"].to(torch.float32)]).tolist()
+        if st[9] != 0 or st[8] != steps:
+            raise _lib.MgxError("graph_train: the Adam schedule cursor ended at {%d, %d} after %d steps"
+                                % (st[8], st[9], steps))
+        return st[:8]

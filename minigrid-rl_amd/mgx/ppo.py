@@ -77,8 +77,13 @@ class PPOConfig:
     graph_collect: bool = False         # with fused_act, compact layout: a whole collect() -- act, step, truncation
                                         # bootstrap (mgx_policy_bootstrap), episode statistics, last values, GAE --
                                         # is one captured graph per ring block, replayed with no host decision
+    graph_train: bool = False           # with fused_update: every epoch of Trainer.train is one captured graph of all
+                                        # its minibatch steps (mgx_adam_step_sched: lr and Adam's bias corrections from
+                                        # a device table), replayed after the permutation is copied in
 
     def __post_init__(self):
+        if self.graph_train and not self.fused_update:
+            raise ValueError("graph_train needs fused_update")
         if self.graph_collect and not (self.fused_act and self.layout == "compact"):
             raise ValueError("graph_collect needs fused_act and layout='compact'")
         if self.fused_mission and not (self.fused_train or self.fused_act):
@@ -407,6 +412,8 @@ class Trainer:
 
     def __init__(self, policy, cfg, group=None):
         self.policy, self.cfg, self.group = policy, cfg, group
+        if getattr(cfg, "graph_train", False) and group is not None:
+            raise ValueError("graph_train does not support a data-parallel group (the all-reduce is not captured)")
         self.lr_schedule = linear_schedule(cfg.initial_learning_rate, cfg.final_learning_rate)
         self.gen = torch.Generator(device=next(policy.parameters()).device)
         self.gen.manual_seed(cfg.seed)
@@ -511,19 +518,28 @@ class Trainer:
         if mode and g_mean is not None:                 # adv_norm="global": the statistics stay on the device
             mode, adv_stats = 2, torch.stack([g_mean, g_std]).float()
         rows = []
+        graph = None
+        if getattr(cfg, "graph_train", False):          # one captured graph per epoch
+            graph = up.graph_begin(buf.buf, rollout, cfg, lr, T * N, adv_mode=mode, adv_stats=adv_stats)
         for epoch in range(cfg.n_epochs):
             perm = perm_fn(T * N) if perm_fn else torch.randperm(T * N, generator=self.gen, device=self.gen.device)
             env, t = perm // T, perm % T
             index = buf.buf.index(t, env).to(torch.int64).contiguous()
             sel = (t * N + env).contiguous()            # the sample's element of the [T, N] rollout arrays
+            if graph is not None:
+                rows.append(up.graph_epoch(graph, index, sel))
+                continue
             stats = torch.zeros(((perm.numel() + bs - 1) // bs, 8), dtype=torch.float32, device=eng.device)
             for i, s in enumerate(range(0, perm.numel(), bs)):
                 m = min(bs, perm.numel() - s)
                 up.step(buf.buf, index[s:s + m], sel[s:s + m], rollout, cfg, lr, stats[i],
                         adv_mode=mode if m > 1 else 0, adv_stats=adv_stats, group=self.group)
             rows.append(stats)
-        up.arena.export_state()
-        st = torch.cat(rows).mean(0).tolist()           # the one host read
+        if graph is not None:
+            st = up.graph_end(rows)                     # the one host read, the schedule cursor with it
+        else:
+            up.arena.export_state()
+            st = torch.cat(rows).mean(0).tolist()       # the one host read
         return dict(pg=st[0], vf=st[1], ent=st[2], kl=st[3], clipfrac=st[4], lr=lr)
 
 
@@ -547,6 +563,8 @@ def learn(cfg, total_timesteps, device="cuda", group=None, rank=0, log=None, cal
     cfg.seed + seed_offset; the learning-rate schedule continues from `timesteps`."""
     from .policy import ActorCriticPolicy
     init = init or {}
+    if getattr(cfg, "graph_train", False) and group is not None:
+        raise ValueError("graph_train does not support a data-parallel group (the all-reduce is not captured)")
     torch.manual_seed(cfg.seed + rank + init.get("seed_offset", 0))
     graph = dict(refill_every=graph_refill_every(cfg.horizon)) if getattr(cfg, "graph_collect", False) else {}
     eng = MgxEngine(n_envs=cfg.n_envs, seed=cfg.seed + init.get("seed_offset", 0), env_index_offset=rank * cfg.n_envs,

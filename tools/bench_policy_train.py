@@ -26,6 +26,13 @@ mgx/fused_update.py) instead, into profiles/r13_ppo_update: the same minibatch s
 on and fused_update off and on in alternation (flag off is the path above, unchanged), the pieces of the on-step
 each on its own, one whole Trainer.train (4 epochs x 16 minibatches) off and on, and the parity ratios of
 tests/test_fused_update_gpu.py's yardstick at the minibatch's and the arena's size.
+
+--graph-train measures the graph-captured update (PPOConfig.graph_train) instead, into
+profiles/r16_graph_train/train.json: one whole Trainer.train with fused_train, fused_mission and fused_update on and
+graph_train off and on, the same build, 12 alternating repeats after the capture, host wall time and device events,
+median (min - max), at (a) the recipe's 16 envs x 1,024 steps, batch 256, 4 epochs and (b) config 3's 65,536 x 16,
+batch 65,536; the six calls of one 256-sample step at (a), each timed on its own; and one learn() iteration
+(collect + train) at (a) with graph_collect and graph_train both on against both off.  No threshold is set: the figures and whether the ranges overlap are recorded as measured.
 """
 import argparse
 import copy
@@ -35,6 +42,7 @@ import os
 import statistics
 import subprocess
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "tests"), os.path.join(ROOT, "minigrid-rl_amd")):
@@ -446,10 +454,158 @@ def part_update_parity(args):
                 worst_ratio_adam_step=worst(adam))
 
 
+GRAPH_REPEATS = 12
+GRAPH_SHAPES = {"a_recipe_16x1024_batch256": dict(n_envs=16, horizon=1024, batch_size=256),
+                "b_config3_65536x16_batch65536": dict(n_envs=65536, horizon=16, batch_size=65536)}
+
+
+def _wall_and_device(fn, torch):
+    """(host wall ms between two device synchronisations, device-event ms) of one fn()."""
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, a.elapsed_time(b)
+
+
+def _off_on(off, on):
+    return dict(off=off, on=on, ranges_overlap=not (on["max_ms"] < off["min_ms"] or off["max_ms"] < on["min_ms"]),
+                on_median_below_off_median=on["median_ms"] < off["median_ms"],
+                ratio_off_over_on=off["median_ms"] / on["median_ms"])
+
+
+def _graph_cfg(shape, **kw):
+    from mgx.ppo import PPOConfig
+    return PPOConfig(n_frames_stack=4, n_epochs=4, env=ENV3, fused_act=True, fused_train=True, fused_mission=True,
+                     fused_update=True, **shape, **kw)
+
+
+def _graph_leg(cfg, torch, refill_every=0):
+    from mgx import MgxEngine
+    from mgx.policy import ActorCriticPolicy
+    from mgx.ppo import Trainer, make_collector
+    torch.manual_seed(0)
+    eng = MgxEngine(n_envs=cfg.n_envs, seed=42, n_stack=4, terminal_mode="truncated", mission_dtype=torch.uint8,
+                    reward64=True, refill_every=refill_every, **ENV3)
+    pol = ActorCriticPolicy(n_stack=4, optim_eps=cfg.optim_eps, mission_cache=True).to(eng.device)
+    col = make_collector(eng, pol, cfg)
+    col.start()
+    return eng, col, Trainer(pol, cfg)
+
+
+def part_graph_train(args):
+    """One Trainer.train on one collected rollout, graph_train off and on in alternation, at both shapes."""
+    import torch
+    out = {}
+    for name, shape in GRAPH_SHAPES.items():
+        legs = {f: _graph_leg(_graph_cfg(shape, graph_train=f), torch) for f in (False, True)}
+        ros = {f: legs[f][1].collect() for f in legs}
+        for _ in range(2):                                           # the first graph leg captures
+            for f in legs:
+                legs[f][2].train(ros[f], 1.0)
+        ms = {f: ([], []) for f in legs}
+        for _ in range(GRAPH_REPEATS):
+            for f in (False, True):
+                w, d = _wall_and_device(lambda: legs[f][2].train(ros[f], 1.0), torch)
+                ms[f][0].append(w)
+                ms[f][1].append(d)
+        for f in legs:
+            legs[f][0].poll_error()
+        up = legs[True][2].update
+        n = shape["n_envs"] * shape["horizon"]
+        out[name] = dict(shape, n_epochs=4, minibatch_steps=4 * ((n + shape["batch_size"] - 1) // shape["batch_size"]),
+                         graphs_captured=len(up._graphs), mission_table_rows=int(up.ev._rows.numel()),
+                         host_wall=_off_on(_stat(ms[False][0]), _stat(ms[True][0])),
+                         device_events=_off_on(_stat(ms[False][1]), _stat(ms[True][1])))
+        del legs, ros
+        torch.cuda.empty_cache()
+    return out
+
+
+def part_graph_pieces(args):
+    """Where a minibatch step of the recipe's shape (256 samples) spends its device time: the six calls of the
+    captured step launched eagerly one at a time on the graph's own buffers, device events, 20 repeats each."""
+    import torch
+    from mgx.fused_update import adam_step_sched, ppo_loss
+    shape = GRAPH_SHAPES["a_recipe_16x1024_batch256"]
+    eng, col, tr = _graph_leg(_graph_cfg(shape, graph_train=True), torch)
+    ro = col.collect()
+    tr.train(ro, 1.0)                                                # captures; index / sel hold the last permutation
+    up, cfg, m = tr.update, tr.cfg, shape["batch_size"]
+    b, enc, ev = up._gbuf, up.ev.mission, up.ev
+    _, stacks, rows, ws = next(iter(up._graphs.values()))
+    index, sel = b["index"][:m], b["sel"][:m]
+    logits, values = b["logits"][:m], b["values"][:m]
+    g_logits, g_values = up._batch[m]
+    rollout = (ro.actions, ro.values, ro.log_probs, ro.advantages, ro.returns)
+    a, pg = up.arena, tr.policy.optimizer.param_groups[0]
+    b["cursor"].zero_()                                              # 256 entries: enough for every call below
+
+    def mission_forward():
+        enc.forward_rows(stacks, up._mission, up.table, rows, ws)
+
+    pieces = dict(
+        mission_forward_rows=mission_forward,
+        policy_act=lambda: ev.forward_raw(ro.buf, index, up._blob, up.table, out=(logits, values)),
+        ppo_loss=lambda: ppo_loss(logits, values, *rollout, cfg.clip_range, cfg.clip_range_vf, cfg.ent_coef, cfg.vf_coef,
+                                  adv_mode=1, sel=sel, out=(g_logits, g_values, b["stats"][0]),
+                                  scratch=up._loss_scratch),
+        policy_backward=lambda: ev.backward_raw(ro.buf, index, up._blob, up.table, g_logits, g_values,
+                                                scratch=b["scratch"], out=(up._g_blob, up.g_table)),
+        # the backward consumes the forward's records: the pair is timed
+        mission_forward_and_backward_rows=lambda: (
+            mission_forward(), enc.backward_rows(stacks, up._mission, up.g_table.view(-1, 128), rows, ws,
+                                                 out=up._g_mission)),
+        adam_step_sched=lambda: adam_step_sched(a.param, a.grad, a.exp_avg, a.exp_avg_sq, b["sched"], b["cursor"],
+                                                betas=pg["betas"], eps=pg["eps"], max_grad_norm=cfg.max_grad_norm,
+                                                scratch=up._adam_scratch))
+    out = {}
+    for name, fn in pieces.items():
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        out[name] = _stat([_timed(fn, torch) for _ in range(20)])
+    eng.poll_error()
+    return dict(shape, mission_table_rows=int(rows.numel()), seq_len=int(stacks.shape[1]), pieces=out)
+
+
+def part_graph_learn(args):
+    """One learn() iteration (collect + train) at the recipe's shape: graph_collect + graph_train both off and both
+    on, the engines alike (the graph collect's refill epoch on both), in alternation after three warm iterations."""
+    import torch
+    from mgx.ppo import graph_refill_every
+    shape = GRAPH_SHAPES["a_recipe_16x1024_batch256"]
+    every = graph_refill_every(shape["horizon"])
+    legs = {f: _graph_leg(_graph_cfg(shape, graph_collect=f, graph_train=f), torch, refill_every=every)
+            for f in (False, True)}
+
+    def iteration(f):
+        _, col, tr = legs[f]
+        tr.train(col.collect(), 1.0)
+
+    for _ in range(3):
+        for f in legs:
+            iteration(f)
+    ms = {f: [] for f in legs}
+    for _ in range(GRAPH_REPEATS):
+        for f in (False, True):
+            ms[f].append(_wall_and_device(lambda: iteration(f), torch)[0])
+    for f in legs:
+        legs[f][0].poll_error()
+    return dict(shape, n_epochs=4, refill_every=every, warm_iterations=3,
+                train_graphs_captured=len(legs[True][2].update._graphs),
+                collect_graphs_captured=len(legs[True][1].graphs),
+                iteration_host_wall=_off_on(_stat(ms[False]), _stat(ms[True])))
+
+
 PARTS = {"step": (part_step, 420), "train": (part_train, 540), "parity": (part_parity, 540),
          "mission_step": (part_mission_step, 420), "mission_parity": (part_mission_parity, 300),
          "update_step": (part_update_step, 300), "update_train": (part_update_train, 420),
-         "update_parity": (part_update_parity, 300)}
+         "update_parity": (part_update_parity, 300), "graph_train": (part_graph_train, 420),
+         "graph_learn": (part_graph_learn, 300), "graph_pieces": (part_graph_pieces, 240)}
 
 
 def main():
@@ -457,6 +613,7 @@ def main():
     ap.add_argument("--out", default=None, help="default: profiles/r10_policy_train (r12_mission_gru with --fused-mission)")
     ap.add_argument("--fused-mission", action="store_true", help="measure the fused mission encoder instead")
     ap.add_argument("--fused-update", action="store_true", help="measure the fused PPO update instead")
+    ap.add_argument("--graph-train", action="store_true", help="measure the graph-captured update instead")
     ap.add_argument("--sha", default=None, help="build id to record (default: git rev-parse HEAD)")
     ap.add_argument("--envs", type=int, default=65536)
     ap.add_argument("--repeats", type=int, default=20)
@@ -470,10 +627,12 @@ def main():
     if args.repeats < 20:
         ap.error("--repeats must be >= 20")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "r13_ppo_update" if args.fused_update else
+        args.out = os.path.join(ROOT, "profiles", "r16_graph_train" if args.graph_train else
+                                "r13_ppo_update" if args.fused_update else
                                 "r12_mission_gru" if args.fused_mission else "r10_policy_train")
     if args.parts is None:
-        args.parts = ("update_parity,update_step,update_train" if args.fused_update else
+        args.parts = ("graph_train,graph_pieces,graph_learn" if args.graph_train else
+                      "update_parity,update_step,update_train" if args.fused_update else
                       "mission_parity,mission_step" if args.fused_mission else "parity,step,train")
     sha = args.sha
     if sha is None:
@@ -504,6 +663,11 @@ def main():
     if "mission_step" in res:
         with open(os.path.join(args.out, "train.json"), "w") as f:
             json.dump(dict(meta, **res["mission_step"]), f, indent=1, sort_keys=True)
+            f.write("\n")
+    if "graph_train" in res or "graph_learn" in res:
+        with open(os.path.join(args.out, "train.json"), "w") as f:
+            json.dump(dict(meta, repeats=GRAPH_REPEATS, train=res.get("graph_train"), learn=res.get("graph_learn"),
+                           step_pieces=res.get("graph_pieces")), f, indent=1, sort_keys=True)
             f.write("\n")
     if "update_parity" in res:
         with open(os.path.join(args.out, "parity.json"), "w") as f:
