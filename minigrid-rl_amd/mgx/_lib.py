@@ -8,7 +8,7 @@ loaded (both carry SONAME libamdhip64.so.7) -- one runtime per process.
 import ctypes
 import os
 
-import torch  # noqa: F401  (see module docstring: load order matters)
+import torch  # before the library is loaded (see module docstring: load order matters)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGX_LIB_PATH", os.path.join(HERE, "libmgx.so"))   # override: diagnostic builds
@@ -234,6 +234,17 @@ def load():
 def check(status, what=""):
     if status != MGX_OK:
         raise MgxError("%s failed (status %d): %s" % (what, status, load().mgx_last_error().decode()))
+
+
+def check_tensor(t, what, dtype, numel, device=None):
+    """`t`, if it is a contiguous tensor of `dtype` with `numel` elements (None: any number) on `device` (None: any):
+    what a library call's wrapper asks of a tensor it passes.  ValueError naming the argument otherwise or if None."""
+    if t is None or t.dtype != dtype or not t.is_contiguous() or numel not in (None, t.numel()) or \
+            (device is not None and t.device != torch.device(device)):
+        raise ValueError("%s must be a contiguous %s tensor%s%s" %
+                         (what, dtype, "" if numel is None else " of %d elements" % numel,
+                          "" if device is None else " on %s" % (device,)))
+    return t
 
 
 def mission_text(mission_id):

@@ -20,6 +20,7 @@ from .fused_policy import _bad, _params
 
 HIDDEN, EMBED, VOCAB = 128, 32, 32
 MAX_ROWS, MAX_SEQ = 2048, 256
+_P = ctypes.c_void_p
 
 
 def mission_params(policy):
@@ -93,79 +94,69 @@ class FusedMissionEncoder:
     def _fill(self, s, tensors):
         s.embedding_dev, s.w_ih_dev, s.w_hh_dev, s.b_ih_dev, s.b_hh_dev = (t.data_ptr() for t in tensors)
 
-    def forward_raw(self, tokens, params, workspace=None):
-        """mgx_mission_forward -> features f32 [n_rows, 128]; params: five contiguous f32 tensors."""
-        n, t = self._check_tokens(tokens)
-        feat = torch.empty((n, HIDDEN), dtype=torch.float32, device=self.device)
-        self._fill(self._p, params)
-        P = ctypes.c_void_p
-        _lib.check(self.L.mgx_mission_forward(P(tokens.data_ptr()), n, t, ctypes.byref(self._p), P(feat.data_ptr()),
-                                              None if workspace is None else P(workspace.data_ptr()),
-                                              0 if workspace is None else workspace.numel(), self._stream()),
-                   "mgx_mission_forward")
-        return feat
+    def _table_args(self, table, rows, n):
+        if table.dim() != 2 or table.shape[1] != HIDDEN:
+            raise ValueError("the table must be a f32 [table_rows, %d] tensor" % HIDDEN)
+        _lib.check_tensor(table, "the table", torch.float32, None, self.device)
+        _lib.check_tensor(rows, "rows", torch.int64, n, self.device)
+        return _P(table.data_ptr()), _P(rows.data_ptr()), table.shape[0]
 
-    def backward_raw(self, tokens, params, g_features, workspace, out=None):
-        """mgx_mission_backward -> the five gradients, shaped as params; `workspace` as forward_raw left it.
-        out: five contiguous f32 tensors of those shapes to write into (mgx/fused_update.py)."""
+    def _forward(self, tokens, params, workspace, table=None, rows=None):
+        """mgx_mission_forward, or with (table, rows) mgx_mission_forward_rows."""
         n, t = self._check_tokens(tokens)
-        g = g_features.to(torch.float32).contiguous()
+        self._fill(self._p, params)
+        head = (_P(tokens.data_ptr()), n, t, ctypes.byref(self._p))
+        tail = (None, 0) if workspace is None else (_P(workspace.data_ptr()), workspace.numel())
+        if table is None:
+            feat = torch.empty((n, HIDDEN), dtype=torch.float32, device=self.device)
+            _lib.check(self.L.mgx_mission_forward(*head, _P(feat.data_ptr()), *tail, self._stream()),
+                       "mgx_mission_forward")
+            return feat
+        _lib.check(self.L.mgx_mission_forward_rows(*head, *self._table_args(table, rows, n), *tail, self._stream()),
+                   "mgx_mission_forward_rows")
+        return table
+
+    def _backward(self, tokens, params, g, workspace, out, rows=None):
+        """mgx_mission_backward on g f32 [n_rows, 128], or with `rows` mgx_mission_backward_rows on the table g."""
+        n, t = self._check_tokens(tokens)
         if out is None:
             grads = tuple(torch.empty_like(p) for p in params)
         else:
             grads = tuple(out)
-            if len(grads) != 5 or any(o.dtype != torch.float32 or not o.is_contiguous() or o.shape != p.shape or
-                                      o.device != p.device for o, p in zip(grads, params)):
+            if len(grads) != 5 or any(o.shape != p.shape for o, p in zip(grads, params)):
                 raise ValueError("out must be five contiguous f32 tensors shaped as params")
+            for i, (o, p) in enumerate(zip(grads, params)):
+                _lib.check_tensor(o, "out[%d]" % i, torch.float32, p.numel(), p.device)
         self._fill(self._p, params)
         self._fill(self._g, grads)
-        P = ctypes.c_void_p
-        _lib.check(self.L.mgx_mission_backward(P(tokens.data_ptr()), n, t, ctypes.byref(self._p), P(g.data_ptr()),
-                                               P(workspace.data_ptr()), workspace.numel(), ctypes.byref(self._g),
-                                               self._stream()), "mgx_mission_backward")
+        head = (_P(tokens.data_ptr()), n, t, ctypes.byref(self._p))
+        tail = (_P(workspace.data_ptr()), workspace.numel(), ctypes.byref(self._g), self._stream())
+        if rows is None:
+            _lib.check(self.L.mgx_mission_backward(*head, _P(g.data_ptr()), *tail), "mgx_mission_backward")
+        else:
+            _lib.check(self.L.mgx_mission_backward_rows(*head, *self._table_args(g, rows, n), *tail),
+                       "mgx_mission_backward_rows")
         return grads
 
-    def _check_table(self, table, rows, n):
-        if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != HIDDEN or \
-                not table.is_contiguous() or table.device != self.device:
-            raise ValueError("the table must be a contiguous f32 [table_rows, %d] tensor on %s" % (HIDDEN, self.device))
-        if rows.dtype != torch.int64 or not rows.is_contiguous() or rows.numel() != n or rows.device != self.device:
-            raise ValueError("rows must be a contiguous i64 tensor of %d elements on %s" % (n, self.device))
+    def forward_raw(self, tokens, params, workspace=None):
+        """mgx_mission_forward -> features f32 [n_rows, 128]; params: five contiguous f32 tensors."""
+        return self._forward(tokens, params, workspace)
+
+    def backward_raw(self, tokens, params, g_features, workspace, out=None):
+        """mgx_mission_backward -> the five gradients, shaped as params; `workspace` as forward_raw left it.
+        out: five contiguous f32 tensors of those shapes to write into (mgx/fused_update.py)."""
+        return self._backward(tokens, params, g_features.to(torch.float32).contiguous(), workspace, out)
 
     def forward_rows(self, tokens, params, table, rows, workspace=None):
         """mgx_mission_forward_rows: row r's feature into table[rows[r]] (table f32 [table_rows, 128], rows i64
         [n_rows]) -- forward_raw + table.index_copy_(0, rows, .) bit for bit, in one launch.  Indices outside the
         table are the caller's error."""
-        n, t = self._check_tokens(tokens)
-        self._check_table(table, rows, n)
-        self._fill(self._p, params)
-        P = ctypes.c_void_p
-        _lib.check(self.L.mgx_mission_forward_rows(
-            P(tokens.data_ptr()), n, t, ctypes.byref(self._p), P(table.data_ptr()), P(rows.data_ptr()),
-            table.shape[0], None if workspace is None else P(workspace.data_ptr()),
-            0 if workspace is None else workspace.numel(), self._stream()), "mgx_mission_forward_rows")
-        return table
+        return self._forward(tokens, params, workspace, table, rows)
 
     def backward_rows(self, tokens, params, g_table, rows, workspace, out=None):
         """mgx_mission_backward_rows: backward_raw on g_table.index_select(0, rows) bit for bit, without the
         index_select (g_table f32 [table_rows, 128]); rows it does not name are not read."""
-        n, t = self._check_tokens(tokens)
-        self._check_table(g_table, rows, n)
-        if out is None:
-            grads = tuple(torch.empty_like(p) for p in params)
-        else:
-            grads = tuple(out)
-            if len(grads) != 5 or any(o.dtype != torch.float32 or not o.is_contiguous() or o.shape != p.shape or
-                                      o.device != p.device for o, p in zip(grads, params)):
-                raise ValueError("out must be five contiguous f32 tensors shaped as params")
-        self._fill(self._p, params)
-        self._fill(self._g, grads)
-        P = ctypes.c_void_p
-        _lib.check(self.L.mgx_mission_backward_rows(
-            P(tokens.data_ptr()), n, t, ctypes.byref(self._p), P(g_table.data_ptr()), P(rows.data_ptr()),
-            g_table.shape[0], P(workspace.data_ptr()), workspace.numel(), ctypes.byref(self._g), self._stream()),
-            "mgx_mission_backward_rows")
-        return grads
+        return self._backward(tokens, params, g_table, workspace, out, rows)
 
     def encode(self, tokens_u8):
         """f32 [n_rows, 128]: the extractor's output on u8 [n_rows, seq_len] token rows.  Under autograd the result

@@ -155,6 +155,28 @@ def sample_addr(engine, buf, index, terminal=None):
     return addr + (P(buf.terminal_rows.data_ptr()) if terminal else None,)
 
 
+def fill_policy(p, blob, mission_feat, mode, seed=0, counter=None):
+    """Fill the MgxPolicy `p`: the weights, the mode and, for the sampling mode, the stream's seed and counter."""
+    p.blob_dev, p.mission_feat_dev = blob.data_ptr(), mission_feat.data_ptr()
+    p.mode, p.seed, p.counter_dev = int(mode), seed, None if counter is None else counter.data_ptr()
+    return p
+
+
+def policy_act(engine, buf, index, p, o, values, actions=None, log_probs=None, logits=None, terminal=False):
+    """mgx_policy_act on the samples `index` (i64, contiguous) of `buf`; p: the MgxPolicy as fill_policy left it; o: the
+    MgxActOut to fill.  actions i64 [n] and log_probs f32 [n] only in modes 1 and 2; logits f32 [n, 7] optional."""
+    n, dev, f32 = index.numel(), engine.device, torch.float32
+    o.actions_dev = o.log_probs_dev = o.logits_dev = None
+    o.values_dev = _lib.check_tensor(values, "values", f32, n, dev).data_ptr()
+    if p.mode:
+        o.actions_dev = _lib.check_tensor(actions, "actions", torch.int64, n, dev).data_ptr()
+        o.log_probs_dev = _lib.check_tensor(log_probs, "log_probs", f32, n, dev).data_ptr()
+    if logits is not None:
+        o.logits_dev = _lib.check_tensor(logits, "logits", f32, n * N_ACTIONS, dev).data_ptr()
+    _lib.check(engine.L.mgx_policy_act(*sample_addr(engine, buf, index, bool(terminal)), ctypes.byref(p),
+                                       ctypes.byref(o), engine._stream()), "mgx_policy_act")
+
+
 class FusedActor:
     """actions / values / log-probs of `policy` for observations of a CompactBuffer of `engine`, one launch each."""
 
@@ -196,48 +218,30 @@ class FusedActor:
             self.mission_feat.copy_(mission_table(self.policy, self._tokens))
         self.policy.train(was)
 
-    def _check_out(self, t, n, dtype, what):
-        if t.dtype != dtype or t.numel() != n or not t.is_contiguous() or t.device != self.engine.device:
-            raise ValueError("out: %s must be a contiguous %s tensor of %d elements on %s"
-                             % (what, dtype, n, self.engine.device))
-        return t
-
     def _run(self, buf, index, mode, terminal=False, logits=False, out=None):
         """out: (actions, values, log_probs) tensors the kernel writes instead of fresh ones (actions and log_probs
         None in mode 0)."""
         e = self.engine
-        if buf.engine is not e:
+        if buf.engine is not e:            # also for an empty index, which launches nothing
             raise ValueError("the buffer belongs to another engine")
         idx = index.to(torch.int64).contiguous()
         n = idx.numel()
         f32 = dict(dtype=torch.float32, device=e.device)
         if out is not None:
             actions, values, log_probs = out
-            self._check_out(values, n, torch.float32, "values")
-            if mode:
-                self._check_out(actions, n, torch.int64, "actions")
-                self._check_out(log_probs, n, torch.float32, "log_probs")
         else:
             values = torch.empty(n, **f32)
             actions = torch.empty(n, dtype=torch.int64, device=e.device) if mode else None
             log_probs = torch.empty(n, **f32) if mode else None
         lg = torch.empty((n, N_ACTIONS), **f32) if logits else None
-        if n == 0:
-            return actions, values, log_probs, lg
-        p, o = self._pol, self._out
-        p.blob_dev, p.mission_feat_dev = self.blob.data_ptr(), self.mission_feat.data_ptr()
-        p.mode, p.seed, p.counter_dev = int(mode), self.seed, self.counter.data_ptr()
-        o.actions_dev = None if actions is None else actions.data_ptr()
-        o.values_dev = values.data_ptr()
-        o.log_probs_dev = None if log_probs is None else log_probs.data_ptr()
-        o.logits_dev = None if lg is None else lg.data_ptr()
-        _lib.check(e.L.mgx_policy_act(*sample_addr(e, buf, idx, bool(terminal)), ctypes.byref(p), ctypes.byref(o),
-                                      e._stream()), "mgx_policy_act")
+        if n:
+            p = fill_policy(self._pol, self.blob, self.mission_feat, mode, self.seed, self.counter)
+            policy_act(e, buf, idx, p, self._out, values, actions, log_probs, lg, terminal=terminal)
         return actions, values, log_probs, lg
 
     def index_table(self, buf):
         """i64 [R, N]: row r holds the flat indices r * N + env of every env.  Once made for `buf`, act / values
-        over all envs take their index from it (a view, no kernel): what a captured collect uses."""
+        over all envs take their index from it (a view, no kernel): what every fused collect uses."""
         if self._table is None or self._table[0] is not buf:
             tab = torch.arange(buf.R * buf.N, dtype=torch.int64, device=self.engine.device).view(buf.R, buf.N)
             self._table = (buf, tab)
@@ -271,13 +275,10 @@ class FusedActor:
         if buf.engine is not e:
             raise ValueError("the buffer belongs to another engine")
         n = buf.N
-        r = buf.rewards[t] if rewards is None else rewards
-        self._check_out(r, n, torch.float32, "rewards")
+        r = _lib.check_tensor(buf.rewards[t] if rewards is None else rewards, "rewards", torch.float32, n, e.device)
         if values is not None:
-            self._check_out(values, n, torch.float32, "values")
-        p, b = self._pol, self._boot
-        p.blob_dev, p.mission_feat_dev = self.blob.data_ptr(), self.mission_feat.data_ptr()
-        p.mode, p.seed, p.counter_dev = 0, self.seed, self.counter.data_ptr()
+            _lib.check_tensor(values, "values", torch.float32, n, e.device)
+        b, p = self._boot, fill_policy(self._pol, self.blob, self.mission_feat, 0, self.seed, self.counter)
         b.truncated_dev, b.terminated_dev = buf.truncated[t].data_ptr(), buf.terminated[t].data_ptr()
         b.rewards_dev, b.gamma = r.data_ptr(), float(gamma)
         b.list_dev, b.count_dev = self.boot_list.data_ptr(), self.boot_count.data_ptr()

@@ -19,7 +19,8 @@ import ctypes
 import torch
 
 from . import _lib
-from .fused_policy import N_ACTIONS, _params, library_blob_words, mission_token_stacks, sample_addr
+from .fused_policy import (N_ACTIONS, _params, fill_policy, library_blob_words, mission_token_stacks, policy_act,
+                           sample_addr)
 
 
 def differentiable_blob(tensors):
@@ -109,16 +110,7 @@ class FusedEvaluator:
             values = torch.empty(n, dtype=torch.float32, device=e.device)
         else:
             logits, values = out
-            for t, numel in ((logits, n * N_ACTIONS), (values, n)):
-                if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel or t.device != e.device:
-                    raise ValueError("out must be contiguous f32 tensors of %d and %d elements on %s"
-                                     % (n * N_ACTIONS, n, e.device))
-        p, o = self._pol, self._out
-        p.blob_dev, p.mission_feat_dev, p.mode = blob.data_ptr(), mission_feat.data_ptr(), 0
-        o.actions_dev = o.log_probs_dev = None
-        o.values_dev, o.logits_dev = values.data_ptr(), logits.data_ptr()
-        _lib.check(e.L.mgx_policy_act(*sample_addr(e, buf, index, False), ctypes.byref(p), ctypes.byref(o), e._stream()),
-                   "mgx_policy_act")
+        policy_act(e, buf, index, fill_policy(self._pol, blob, mission_feat, 0), self._out, values, logits=logits)
         return logits, values
 
     def backward_raw(self, buf, index, blob, mission_feat, g_logits, g_values, scratch=None, out=None):
@@ -137,10 +129,8 @@ class FusedEvaluator:
             gm = torch.empty((256, k, 128), dtype=torch.float32, device=e.device)
         else:
             gb, gm = out
-            for t, numel in ((gb, self.words), (gm, 256 * k * 128)):
-                if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel or t.device != e.device:
-                    raise ValueError("out must be contiguous f32 tensors of %d and %d elements on %s"
-                                     % (self.words, 256 * k * 128, e.device))
+            _lib.check_tensor(gb, "out: grad_blob", torch.float32, self.words, e.device)
+            _lib.check_tensor(gm, "out: grad_mission_feat", torch.float32, 256 * k * 128, e.device)
         g = self._grad
         g.blob_dev, g.mission_feat_dev = blob.data_ptr(), mission_feat.data_ptr()
         g.g_logits_dev, g.g_values_dev = gl.data_ptr(), gv.data_ptr()

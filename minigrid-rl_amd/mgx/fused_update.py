@@ -11,12 +11,13 @@ ParamArena is the storage that makes this possible: the 25 parameter tensors bec
 .grad views of a second one, Adam's moments two more.  mgx_policy_backward and mgx_mission_backward write their
 gradients straight into the gradient buffer; mgx_adam_step clips and steps the whole buffer in two launches.
 
-Graph-captured update (PPOConfig.graph_train).  The step above is a fixed sequence of launches, but
-mgx_adam_step takes lr and the bias corrections by value, so a captured graph would bake them in.
-mgx_adam_step_sched reads them from a device table at a device-side cursor, and mgx_mission_forward_rows /
-mgx_mission_backward_rows address the mission table in place (no index_copy_ / index_select), so FusedUpdate captures
-one graph of a whole epoch -- every minibatch on fixed slices of persistent index / sel buffers -- and Trainer.train
-replays it once per epoch: per epoch the host draws the permutation, copies it in and launches one graph.
+The step exists once, as FusedUpdate._minibatch: six launches on persistent memory; its callers pass what differs
+(index / sel, the statistics row, the mission workspace, the policy-gradient scratch, the Adam call).
+
+Graph-captured update (PPOConfig.graph_train).  mgx_adam_step takes lr and the bias corrections by
+value, so a captured graph would bake them in; mgx_adam_step_sched reads them from a device table at a device-side
+cursor.  With it FusedUpdate captures one graph of a whole epoch -- _minibatch on fixed slices of persistent index /
+sel buffers -- and Trainer.train replays it once per epoch: the host draws the permutation, copies it in and launches.
 """
 import ctypes
 
@@ -38,12 +39,6 @@ def _ptr(t):
 
 def _stream(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _f32(t, numel, what):
-    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel:
-        raise ValueError("%s must be a contiguous f32 tensor of %d elements" % (what, numel))
-    return t
 
 
 def arena_layout(n_stack):
@@ -138,24 +133,23 @@ def ppo_loss(logits, values, actions, old_values, old_log_probs, advantages, ret
     L = _lib.load()
     n = values.numel()
     dev = logits.device
-    _f32(logits, n * N_ACTIONS, "logits")
-    _f32(values, n, "values")
+    f32, check = torch.float32, _lib.check_tensor
+    check(logits, "logits", f32, n * N_ACTIONS)
+    check(values, "values", f32, n)
     for t in (old_values, old_log_probs, advantages, returns):
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError("the rollout arrays must be contiguous f32 tensors")
-    if actions.dtype != torch.int64 or not actions.is_contiguous():
-        raise ValueError("actions must be a contiguous i64 tensor")
-    if sel is not None and (sel.dtype != torch.int64 or not sel.is_contiguous() or sel.numel() != n):
-        raise ValueError("sel must be a contiguous i64 tensor of %d elements" % n)
+        check(t, "a rollout array", f32, None)
+    check(actions, "actions", torch.int64, None)
+    if sel is not None:
+        check(sel, "sel", torch.int64, n)
     if sel is None and min(t.numel() for t in (actions, old_values, old_log_probs, advantages, returns)) < n:
         raise ValueError("the rollout arrays are shorter than the batch")
     if out is None:
         out = (torch.empty((n, N_ACTIONS), dtype=torch.float32, device=dev),
                torch.empty(n, dtype=torch.float32, device=dev), torch.empty(8, dtype=torch.float32, device=dev))
     g_logits, g_values, stats = out
-    _f32(g_logits, n * N_ACTIONS, "g_logits")
-    _f32(g_values, n, "g_values")
-    _f32(stats, 8, "stats")
+    check(g_logits, "g_logits", f32, n * N_ACTIONS)
+    check(g_values, "g_values", f32, n)
+    check(stats, "stats", f32, 8)
     if scratch is None:
         scratch = torch.empty(max(int(L.mgx_ppo_loss_scratch_words(n)), 2), dtype=torch.float32, device=dev)
     a = _lib.MgxPpoLossArgs(
@@ -171,21 +165,35 @@ def ppo_loss(logits, values, actions, old_values, old_log_probs, advantages, ret
     return out
 
 
-def adam_step(param, grad, exp_avg, exp_avg_sq, lr, step, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0,
-              grad_scale=1.0, total_norm=None, scratch=None):
-    """mgx_adam_step on four flat contiguous f32 tensors of one length, in place; `step` counts from 1.
-    total_norm: optional f32 [1] for the norm before the clip."""
+def _adam(param, grad, exp_avg, exp_avg_sq, lr, step, sched, betas, eps, max_grad_norm, grad_scale, total_norm,
+          scratch):
+    """mgx_adam_step with (lr, step) by value, or with sched = (table, cursor) mgx_adam_step_sched."""
     L = _lib.load()
-    n = param.numel()
+    n, dev = param.numel(), param.device
     for t, what in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        _f32(t, n, what)
-    dev = param.device
+        _lib.check_tensor(t, what, torch.float32, n)
     if scratch is None:
         scratch = torch.empty(max(int(L.mgx_adam_scratch_words(n)), 2), dtype=torch.float32, device=dev)
     a = _lib.MgxAdamArgs(lr=float(lr), beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps), step=int(step),
                          max_grad_norm=float(max_grad_norm) if max_grad_norm else 0.0, grad_scale=float(grad_scale))
-    _lib.check(L.mgx_adam_step(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), n, ctypes.byref(a),
-                               _ptr(total_norm), _ptr(scratch), scratch.numel(), _stream(dev)), "mgx_adam_step")
+    head = (_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), n, ctypes.byref(a))
+    tail = (_ptr(total_norm), _ptr(scratch), scratch.numel(), _stream(dev))
+    if sched is None:
+        _lib.check(L.mgx_adam_step(*head, *tail), "mgx_adam_step")
+        return
+    table, cursor = sched
+    if table.dim() != 2 or table.shape[1] != 2:
+        raise ValueError("table must be a f32 [len, 2] tensor")
+    _lib.check_tensor(table, "table", torch.float32, None, dev)
+    _lib.check_tensor(cursor, "cursor", torch.int32, 2, dev)
+    _lib.check(L.mgx_adam_step_sched(*head, _ptr(table), table.shape[0], _ptr(cursor), *tail), "mgx_adam_step_sched")
+
+
+def adam_step(param, grad, exp_avg, exp_avg_sq, lr, step, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0,
+              grad_scale=1.0, total_norm=None, scratch=None):
+    """mgx_adam_step on four flat contiguous f32 tensors of one length, in place; `step` counts from 1.
+    total_norm: optional f32 [1] for the norm before the clip."""
+    _adam(param, grad, exp_avg, exp_avg_sq, lr, step, None, betas, eps, max_grad_norm, grad_scale, total_norm, scratch)
 
 
 def adam_schedule(lrs, first_step, betas=(0.9, 0.999), eps=1e-8):
@@ -207,23 +215,8 @@ def adam_step_sched(param, grad, exp_avg, exp_avg_sq, table, cursor, betas=(0.9,
     """mgx_adam_step_sched: adam_step whose (lr, step) come from the device: table f32 [len, 2] as adam_schedule
     returns it, cursor i32 [2] = {next entry, overrun count}.  Past the table's end nothing is updated and cursor[1]
     counts the call."""
-    L = _lib.load()
-    n = param.numel()
-    for t, what in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        _f32(t, n, what)
-    dev = param.device
-    if table.dtype != torch.float32 or not table.is_contiguous() or table.dim() != 2 or table.shape[1] != 2 or \
-            table.device != dev:
-        raise ValueError("table must be a contiguous f32 [len, 2] tensor on %s" % (dev,))
-    if cursor.dtype != torch.int32 or not cursor.is_contiguous() or cursor.numel() != 2 or cursor.device != dev:
-        raise ValueError("cursor must be a contiguous i32 [2] tensor on %s" % (dev,))
-    if scratch is None:
-        scratch = torch.empty(max(int(L.mgx_adam_scratch_words(n)), 2), dtype=torch.float32, device=dev)
-    a = _lib.MgxAdamArgs(lr=0.0, beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps), step=0,
-                         max_grad_norm=float(max_grad_norm) if max_grad_norm else 0.0, grad_scale=float(grad_scale))
-    _lib.check(L.mgx_adam_step_sched(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), n, ctypes.byref(a),
-                                     _ptr(table), table.shape[0], _ptr(cursor), _ptr(total_norm), _ptr(scratch),
-                                     scratch.numel(), _stream(dev)), "mgx_adam_step_sched")
+    _adam(param, grad, exp_avg, exp_avg_sq, 0.0, 0, (table, cursor), betas, eps, max_grad_norm, grad_scale,
+          total_norm, scratch)
 
 
 MAX_GRAPHS = 8                         # captured epoch graphs kept per FusedUpdate; the oldest is evicted
@@ -231,14 +224,14 @@ MAX_GRAPHS = 8                         # captured epoch graphs kept per FusedUpd
 
 class FusedUpdate:
     """One PPO minibatch step of `policy` on samples of a CompactBuffer of `engine` without torch.autograd:
-    mgx_mission_forward, mgx_policy_act (mode 0), mgx_ppo_loss, mgx_policy_backward, mgx_mission_backward,
-    mgx_adam_step on a ParamArena.  Adam's betas and eps are policy.optimizer's; weight decay, amsgrad and
-    maximize are not supported (ValueError)."""
+    mgx_mission_forward_rows, mgx_policy_act (mode 0), mgx_ppo_loss, mgx_policy_backward, mgx_mission_backward_rows
+    and Adam on a ParamArena -- _minibatch, which step() runs at once and _capture_epoch captures.  Adam's betas and
+    eps are policy.optimizer's; weight decay, amsgrad and maximize are not supported (ValueError)."""
 
     def __init__(self, policy, engine, max_groups=0):
         from .fused_train import FusedEvaluator
         mission_params(policy)                           # ValueError before anything touches the device
-        self.ev =FusedEvaluator(policy, engine, max_groups=max_groups, fused_mission=True)   # ValueError first
+        self.ev = FusedEvaluator(policy, engine, max_groups=max_groups, fused_mission=True)   # ValueError first
         g = policy.optimizer.param_groups
         if len(g) != 1 or g[0].get("weight_decay", 0) or g[0].get("amsgrad", False) or g[0].get("maximize", False):
             raise ValueError("FusedUpdate supports torch.optim.Adam's default update in one parameter group only")
@@ -252,7 +245,7 @@ class FusedUpdate:
         self._adam_scratch = torch.empty(int(L.mgx_adam_scratch_words(self.arena.words)), dtype=torch.float32,
                                          device=dev)
         self._loss_scratch = torch.empty(int(L.mgx_ppo_loss_scratch_words(1 << 30)), dtype=torch.float32, device=dev)
-        self._batch = {}               # B -> (g_logits, g_values)
+        self._batch = {}               # B -> (logits, values, g_logits, g_values), see _buffers
         self._graphs = {}              # graph_train: cache key -> (graph, stacks, rows, workspace), oldest first
         self._gbuf = None              # graph_train: the persistent buffers of one (T * N, minibatch sizes, epochs)
         self._gstream = None
@@ -273,39 +266,62 @@ class FusedUpdate:
         if not self.arena.attached():
             raise RuntimeError("FusedUpdate: the policy's parameters are no longer views of the arena")
 
-    def step(self, buf, index, sel, rollout, cfg, lr, stats_out, adv_mode=1, adv_stats=None, group=None):
-        """One minibatch.  index: i64 [B] flat compact-buffer indices (CompactBuffer.index); sel: i64 [B], the
-        element of the rollout arrays each sample reads; rollout: (actions, old_values, old_log_probs, advantages,
-        returns); cfg: clip_range, clip_range_vf, ent_coef, vf_coef, max_grad_norm; stats_out: f32 [8] row that
-        receives mgx_ppo_loss' statistics; group: all-reduce the gradient arena (mean) before the step."""
-        ev, a, enc = self.ev, self.arena, self.ev.mission
-        n = index.numel()
+    def _buffers(self, n):
+        """(logits, values, g_logits, g_values) of n samples: made once per size and kept (graphs address them)."""
         if n not in self._batch:
-            dev = self.engine.device
-            self._batch[n] = (torch.empty((n, N_ACTIONS), dtype=torch.float32, device=dev),
-                              torch.empty(n, dtype=torch.float32, device=dev))
-        g_logits, g_values = self._batch[n]
+            f32 = dict(dtype=torch.float32, device=self.engine.device)
+            self._batch[n] = (torch.empty((n, N_ACTIONS), **f32), torch.empty(n, **f32),
+                              torch.empty((n, N_ACTIONS), **f32), torch.empty(n, **f32))
+        return self._batch[n]
+
+    def _minibatch(self, buf, index, sel, rollout, cfg, adv_mode, adv_stats, *, stats_out, workspace, scratch, adam):
+        """The six launches of one minibatch, the same whether they run now or are being captured.  workspace: the
+        mission step records; scratch: mgx_policy_backward's (None: the evaluator's own, grown on demand); adam: the
+        sixth launch as a call without arguments, _adam_by_value or _adam_by_schedule bound to what it needs."""
+        ev, enc = self.ev, self.ev.mission
+        logits, values, g_logits, g_values = self._buffers(index.numel())
         stacks, rows = ev._stacks, ev._rows
-        ws = enc._workspace(stacks.shape[0], stacks.shape[1])
-        enc._ticket += 1               # a pending autograd encode() of this encoder loses the workspace
-        feat = enc.forward_raw(stacks, self._mission, ws)
-        self.table.index_copy_(0, rows, feat)
-        logits, values = ev.forward_raw(buf, index, self._blob, self.table)
+        enc.forward_rows(stacks, self._mission, self.table, rows, workspace)
+        ev.forward_raw(buf, index, self._blob, self.table, out=(logits, values))
         ppo_loss(logits, values, *rollout, cfg.clip_range, cfg.clip_range_vf, cfg.ent_coef, cfg.vf_coef,
                  adv_mode=adv_mode, sel=sel, adv_stats=adv_stats, out=(g_logits, g_values, stats_out),
                  scratch=self._loss_scratch)
-        ev.backward_raw(buf, index, self._blob, self.table, g_logits, g_values, out=(self._g_blob, self.g_table))
-        g_feat = self.g_table.view(-1, 128).index_select(0, rows)
-        enc.backward_raw(stacks, self._mission, g_feat, ws, out=self._g_mission)
+        ev.backward_raw(buf, index, self._blob, self.table, g_logits, g_values, scratch=scratch,
+                        out=(self._g_blob, self.g_table))
+        enc.backward_rows(stacks, self._mission, self.g_table.view(-1, 128), rows, workspace, out=self._g_mission)
+        adam()
+
+    def _adam_args(self, cfg):
+        a, pg = self.arena, self.policy.optimizer.param_groups[0]
+        return (a.param, a.grad, a.exp_avg, a.exp_avg_sq), dict(
+            betas=pg["betas"], eps=pg["eps"], max_grad_norm=cfg.max_grad_norm, total_norm=self.total_norm,
+            scratch=self._adam_scratch)
+
+    def _adam_by_value(self, cfg, lr, group):
+        """All-reduce the gradient arena over `group` (the mean, through grad_scale), count arena.step, step at lr."""
         scale = 1.0
         if group is not None:
-            torch.distributed.all_reduce(a.grad, group=group)
+            torch.distributed.all_reduce(self.arena.grad, group=group)
             scale = 1.0 / torch.distributed.get_world_size(group)
-        a.step += 1
-        pg = self.policy.optimizer.param_groups[0]
-        adam_step(a.param, a.grad, a.exp_avg, a.exp_avg_sq, lr, a.step, betas=pg["betas"], eps=pg["eps"],
-                  max_grad_norm=cfg.max_grad_norm, grad_scale=scale, total_norm=self.total_norm,
-                  scratch=self._adam_scratch)
+        self.arena.step += 1
+        bufs, kw = self._adam_args(cfg)
+        adam_step(*bufs, lr, self.arena.step, grad_scale=scale, **kw)
+
+    def _adam_by_schedule(self, cfg, table, cursor):
+        """(lr, step) from `table` at `cursor` on the device; graph_end counts the steps."""
+        bufs, kw = self._adam_args(cfg)
+        adam_step_sched(*bufs, table, cursor, **kw)
+
+    def step(self, buf, index, sel, rollout, cfg, lr, stats_out, adv_mode=1, adv_stats=None, group=None):
+        """One minibatch, now.  index: i64 [B] flat compact-buffer indices (CompactBuffer.index); sel: i64 [B], the
+        element of the rollout arrays each sample reads; rollout: (actions, old_values, old_log_probs, advantages,
+        returns); cfg: clip_range, clip_range_vf, ent_coef, vf_coef, max_grad_norm; stats_out: f32 [8] row that
+        receives mgx_ppo_loss' statistics; group: all-reduce the gradient arena (mean) before the step."""
+        enc, stacks = self.ev.mission, self.ev._stacks
+        ws = enc._workspace(stacks.shape[0], stacks.shape[1])
+        enc._ticket += 1               # a pending autograd encode() of this encoder loses the workspace
+        self._minibatch(buf, index, sel, rollout, cfg, adv_mode, adv_stats, stats_out=stats_out, workspace=ws,
+                        scratch=None, adam=lambda: self._adam_by_value(cfg, lr, group))
 
     # ---- graph_train: one captured graph per epoch (DESIGN.md §4.11)
     def _graph_buffers(self, n, sizes, n_epochs):
@@ -321,44 +337,20 @@ class FusedUpdate:
             index=torch.zeros(n, dtype=torch.int64, device=dev), sel=torch.zeros(n, dtype=torch.int64, device=dev),
             stats=torch.zeros((len(sizes), 8), **f32), adv_stats=torch.zeros(2, **f32),
             sched=torch.zeros((n_epochs * len(sizes), 2), **f32), cursor=torch.zeros(2, dtype=torch.int32, device=dev),
-            logits=torch.empty((top, N_ACTIONS), **f32), values=torch.empty(top, **f32),
             scratch=torch.empty(int(L.mgx_policy_grad_scratch_words(self.ev.K, top, self.ev.max_groups)), **f32))
         if self._gstream is None:
             self._gstream = torch.cuda.Stream(dev)
         return self._gbuf
 
-    def _graph_step(self, b, buf, s, m, i, rollout, cfg, adv_mode, stacks, rows, ws):
-        """FusedUpdate.step on the fixed slice [s, s + m) of the persistent index / sel, every launch on persistent
-        memory: mgx_mission_forward_rows, mgx_policy_act, mgx_ppo_loss, mgx_policy_backward,
-        mgx_mission_backward_rows, mgx_adam_step_sched."""
-        ev, a, enc = self.ev, self.arena, self.ev.mission
-        if m not in self._batch:
-            raise RuntimeError("FusedUpdate: no gradient buffers for a minibatch of %d" % m)
-        g_logits, g_values = self._batch[m]
-        index, sel = b["index"][s:s + m], b["sel"][s:s + m]
-        enc.forward_rows(stacks, self._mission, self.table, rows, ws)
-        ev.forward_raw(buf, index, self._blob, self.table, out=(b["logits"][:m], b["values"][:m]))
-        ppo_loss(b["logits"][:m], b["values"][:m], *rollout, cfg.clip_range, cfg.clip_range_vf, cfg.ent_coef,
-                 cfg.vf_coef, adv_mode=adv_mode, sel=sel, adv_stats=b["adv_stats"] if adv_mode == 2 else None,
-                 out=(g_logits, g_values, b["stats"][i]), scratch=self._loss_scratch)
-        ev.backward_raw(buf, index, self._blob, self.table, g_logits, g_values, scratch=b["scratch"],
-                        out=(self._g_blob, self.g_table))
-        enc.backward_rows(stacks, self._mission, self.g_table.view(-1, 128), rows, ws, out=self._g_mission)
-        pg = self.policy.optimizer.param_groups[0]
-        adam_step_sched(a.param, a.grad, a.exp_avg, a.exp_avg_sq, b["sched"], b["cursor"], betas=pg["betas"],
-                        eps=pg["eps"], max_grad_norm=cfg.max_grad_norm, total_norm=self.total_norm,
-                        scratch=self._adam_scratch)
-
     def _capture_epoch(self, b, buf, rollout, cfg, adv_mode):
-        """Capture one epoch -- every minibatch's launches in order on one stream, none executed."""
-        ev, enc, dev = self.ev, self.ev.mission, self.engine.device
-        stacks, rows = ev._stacks, ev._rows
+        """Capture one epoch -- every minibatch's launches in order on one stream, none executed: _minibatch on the
+        fixed slices [s, s + m) of the persistent index / sel."""
+        enc, dev = self.ev.mission, self.engine.device
+        stacks, rows = self.ev._stacks, self.ev._rows
         ws = torch.empty(int(enc.L.mgx_mission_workspace_words(stacks.shape[0], stacks.shape[1])),
                          dtype=torch.float32, device=dev)          # the graph's own: enc's is reallocated as it grows
         for m in set(b["shape"][1]):
-            if m not in self._batch:
-                self._batch[m] = (torch.empty((m, N_ACTIONS), dtype=torch.float32, device=dev),
-                                  torch.empty(m, dtype=torch.float32, device=dev))
+            self._buffers(m)           # nothing is allocated under capture
         torch.cuda.synchronize(dev)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.stream(self._gstream):
@@ -366,7 +358,11 @@ class FusedUpdate:
             try:
                 s = 0
                 for i, m in enumerate(b["shape"][1]):
-                    self._graph_step(b, buf, s, m, i, rollout, cfg, adv_mode if m > 1 else 0, stacks, rows, ws)
+                    mode = adv_mode if m > 1 else 0
+                    self._minibatch(buf, b["index"][s:s + m], b["sel"][s:s + m], rollout, cfg, mode,
+                                    b["adv_stats"] if mode == 2 else None, stats_out=b["stats"][i], workspace=ws,
+                                    scratch=b["scratch"],
+                                    adam=lambda: self._adam_by_schedule(cfg, b["sched"], b["cursor"]))
                     s += m
             finally:
                 g.capture_end()

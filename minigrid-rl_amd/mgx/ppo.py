@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 from .compact import CompactBuffer
-from .engine import MgxEngine, gae, gae_dones
+from .engine import MgxEngine, _stats_scratch, gae, gae_dones
 
 
 @dataclass
@@ -82,6 +82,8 @@ class PPOConfig:
                                         # a device table), replayed after the permutation is copied in
 
     def __post_init__(self):
+        if self.fused_train and self.layout != "compact":
+            raise ValueError("fused_train needs layout='compact'")
         if self.graph_train and not self.fused_update:
             raise ValueError("graph_train needs fused_update")
         if self.graph_collect and not (self.fused_act and self.layout == "compact"):
@@ -103,6 +105,20 @@ def linear_schedule(initial_value, final_value):
     def func(progress_remaining):
         return max(progress_remaining * initial_value, final_value)
     return func
+
+
+def check_group(cfg, group):
+    """The one flag rule that needs a process group."""
+    if cfg.graph_train and group is not None:
+        raise ValueError("graph_train does not support a data-parallel group (the all-reduce is not captured)")
+
+
+def minibatch_env_t(perm, batch_size, T):
+    """(env, t) of every minibatch of `perm`, a permutation of the env-major flat index i = env * T + t (SB3
+    swap_and_flatten), in slices of batch_size; the last one may be shorter."""
+    for s in range(0, perm.numel(), batch_size):
+        idx = perm[s:s + batch_size]
+        yield idx // T, idx % T
 
 
 class RolloutBuffer:
@@ -141,10 +157,7 @@ class RolloutBuffer:
 
     def minibatches(self, batch_size, perm):
         """perm: permutation of the env-major flat index i = env * T + t (SB3 swap_and_flatten)."""
-        T = self.T
-        for s in range(0, perm.numel(), batch_size):
-            idx = perm[s:s + batch_size]
-            env, t = idx // T, idx % T
+        for env, t in minibatch_env_t(perm, batch_size, self.T):
             obs = {"image": self.image[t, env], "direction": self.direction[t, env], "mission": self.mission[t, env]}
             yield (obs, self.actions[t, env], self.values[t, env], self.log_probs[t, env],
                    self.advantages[t, env], self.returns[t, env])
@@ -239,10 +252,7 @@ class CompactRollout:
     def minibatches(self, batch_size, perm):
         """perm: permutation of the env-major flat index i = env * T + t (SB3 swap_and_flatten);
         observations gathered straight into the policy's f32 input."""
-        T = self.T
-        for s in range(0, perm.numel(), batch_size):
-            idx = perm[s:s + batch_size]
-            env, t = idx // T, idx % T
+        for env, t in minibatch_env_t(perm, batch_size, self.T):
             obs = self.buf.gather(self.buf.index(t, env), f32=True)
             yield (obs, self.actions[t, env], self.values[t, env], self.log_probs[t, env],
                    self.advantages[t, env], self.returns[t, env])
@@ -250,10 +260,7 @@ class CompactRollout:
     def minibatch_indices(self, batch_size, perm):
         """minibatches() without the gather: the observations named by their flat compact-buffer indices
         (CompactBuffer.index), for FusedEvaluator.evaluate_actions."""
-        T = self.T
-        for s in range(0, perm.numel(), batch_size):
-            idx = perm[s:s + batch_size]
-            env, t = idx // T, idx % T
+        for env, t in minibatch_env_t(perm, batch_size, self.T):
             yield (self.buf.index(t, env), self.actions[t, env], self.values[t, env], self.log_probs[t, env],
                    self.advantages[t, env], self.returns[t, env])
 
@@ -262,7 +269,8 @@ class CompactRolloutCollector:
     """OnPolicyAlgorithm.collect_rollouts over an MgxEngine with the compact layout: per step one
     gather builds the policy's f32 input (VecFrameStack + preprocess_obs fused), one
     mgx_step_compact writes the next observation row, reward and done straight into the rollout
-    buffer (no stack roll, no buffer copy)."""
+    buffer (no stack roll, no buffer copy).  With cfg.fused_act the step is _fused_step, whether
+    collect() runs it step by step or, with cfg.graph_collect, replays a captured horizon of it."""
 
     def __init__(self, engine, policy, cfg):
         self.engine, self.policy, self.cfg = engine, policy, cfg
@@ -271,28 +279,24 @@ class CompactRolloutCollector:
         self.ep_returns, self.ep_lens = [], []
         self.stopped = False
         self._n_rollouts = 0
+        T, N, k, dev = cfg.horizon, engine.n, engine.n_stack, engine.device
+        f32 = dict(dtype=torch.float32, device=dev)
         self.fused = None
-        if getattr(cfg, "fused_act", False):
-            from .fused_policy import FusedActor
-            self.fused = FusedActor(policy, engine, seed=cfg.seed, fused_mission=getattr(cfg, "fused_mission", False))
         self.graphs = None                 # cfg.graph_collect: one captured collect per ring block, made on first use
-        if getattr(cfg, "graph_collect", False):
-            if self.fused is None:
-                raise ValueError("graph_collect needs fused_act")
-            if engine.ring_depth > 0 and cfg.horizon % engine.refill_every:
-                raise ValueError("graph_collect: the horizon (%d) must be a multiple of the engine's refill epoch "
-                                 "(refill_every = %d)" % (cfg.horizon, engine.refill_every))
-            self.graphs = {}
-            T, N = cfg.horizon, engine.n
-            f32 = dict(dtype=torch.float32, device=engine.device)
+        if cfg.fused_act:
+            from .fused_policy import FusedActor
+            self.fused = FusedActor(policy, engine, seed=cfg.seed, fused_mission=cfg.fused_mission)
             self._ep_r, self._ep_l = torch.zeros((T, N), **f32), torch.zeros((T, N), **f32)
             self._last_values = torch.zeros(N, **f32)
             self._nan = torch.full((), math.nan, **f32)     # torch.where(..., out=) takes no scalar
-            self._stream = torch.cuda.Stream(engine.device)
-        n, k, dev = engine.n, engine.n_stack, engine.device
-        self._obs = dict(image=torch.empty((n, 3 * k, 7, 7), dtype=torch.float32, device=dev),
-                         direction=torch.empty((n, 4 * k), dtype=torch.float32, device=dev),
-                         mission=torch.empty((n, 32 * k), dtype=torch.uint8, device=dev))
+        if cfg.graph_collect:
+            if engine.ring_depth > 0 and T % engine.refill_every:
+                raise ValueError("graph_collect: the horizon (%d) must be a multiple of the engine's refill epoch "
+                                 "(refill_every = %d)" % (T, engine.refill_every))
+            self.graphs = {}
+            self._stream = torch.cuda.Stream(dev)
+        self._obs = dict(image=torch.empty((N, 3 * k, 7, 7), **f32), direction=torch.empty((N, 4 * k), **f32),
+                         mission=torch.empty((N, 32 * k), dtype=torch.uint8, device=dev))
 
     def start(self):
         self.engine.reset()
@@ -301,14 +305,10 @@ class CompactRolloutCollector:
 
     @torch.no_grad()
     def collect(self, callback=None):
+        if self.fused is not None:
+            return self._collect_fused(callback)
         e, pol, cfg, ro = self.engine, self.policy, self.cfg, self.rollout
-        buf, fused = ro.buf, self.fused
-        if self.graphs is not None:
-            if callback is not None:
-                raise ValueError("graph_collect: a callback needs a host decision every step")
-            return self._collect_graph()
-        if fused is not None:
-            fused.sync()                   # the optimiser phase since the last rollout changed the weights
+        buf = ro.buf
         if self._n_rollouts:
             buf.carry_over()
         self._n_rollouts += 1
@@ -316,19 +316,12 @@ class CompactRolloutCollector:
         gamma32 = torch.tensor(cfg.gamma, dtype=torch.float32)
         ep_r, ep_l = [], []
         for t in range(cfg.horizon):
-            if fused is not None:
-                actions, values, log_probs = fused.act(buf, t)
-            else:
-                obs = buf.gather_step(t, f32=True, out=self._obs)
-                actions, values, log_probs = pol(obs)
+            actions, values, log_probs = pol(buf.gather_step(t, f32=True, out=self._obs))
             buf.step(t, actions)
-            self.num_timesteps += e.n
+            self.num_timesteps += e.n              # next: the torch policy's bootstrap needs a host read
             boot = (buf.truncated[t].bool() & ~buf.terminated[t].bool()).nonzero().flatten()
             if boot.numel():
-                if fused is not None:
-                    tv = fused.values(buf, t, terminal=True, envs=boot)
-                else:
-                    tv = pol.predict_values(buf.gather_step(t, terminal=True, envs=boot))
+                tv = pol.predict_values(buf.gather_step(t, terminal=True, envs=boot))
                 r = buf.rewards[t]
                 r.index_put_((boot,), r.index_select(0, boot) + gamma32.to(tv.device) * tv)
             ro.actions[t].copy_(actions)
@@ -342,26 +335,37 @@ class CompactRolloutCollector:
                     self.stopped = True
                     return None
                 pol.train(False)
-        if fused is not None:
-            last_values = fused.values(buf, cfg.horizon)
-        else:
-            last_values = pol.predict_values(buf.gather_step(cfg.horizon, f32=True, out=self._obs))
+        last_values = pol.predict_values(buf.gather_step(cfg.horizon, f32=True, out=self._obs))
         ro.compute_returns_and_advantage(last_values, cfg.gamma, cfg.gae_lambda)
         r, l = torch.stack(ep_r), torch.stack(ep_l)
         m = ~torch.isnan(r)
         self.ep_returns, self.ep_lens = r[m], l[m]
         return ro
 
+    def _fused_step(self, t):
+        """Step t of a fused collect, no launch needing the host: act straight into row t of the rollout arrays, the
+        engine step, the device-side truncation bootstrap, the statistics of the episodes that ended (NaN elsewhere)."""
+        e, ro, fused = self.engine, self.rollout, self.fused
+        buf = ro.buf
+        actions, _, _ = fused.act(buf, t, out=(ro.actions[t], ro.values[t], ro.log_probs[t]))
+        buf.step(t, actions)
+        fused.bootstrap(buf, t, self.cfg.gamma)
+        d = buf.dones[t].bool()
+        torch.where(d, e.ep_return, self._nan, out=self._ep_r[t])
+        torch.where(d, e.ep_len.float(), self._nan, out=self._ep_l[t])
+
+    def _fused_finish(self):
+        """After the last step: the values of the final observation, then GAE."""
+        cfg, ro = self.cfg, self.rollout
+        self.fused.values(ro.buf, cfg.horizon, out=self._last_values)
+        ro.compute_returns_and_advantage(self._last_values, cfg.gamma, cfg.gae_lambda)
 
     def _capture(self):
         """Capture the collect of the current ring block: every launch of a rollout, none executed.  The Python
         bookkeeping the captured calls do (engine.calls) is redone by the caller on every replay."""
-        e, cfg, ro, fused = self.engine, self.cfg, self.rollout, self.fused
-        buf = ro.buf
-        from .engine import _stats_scratch
+        e, cfg, ro = self.engine, self.cfg, self.rollout
         e.join()
         torch.cuda.synchronize(e.device)
-        fused.index_table(buf)
         calls = e.calls
         g = torch.cuda.CUDAGraph()
         with torch.cuda.stream(self._stream):
@@ -369,39 +373,48 @@ class CompactRolloutCollector:
             g.capture_begin()
             ro.adv_stats.zero_()
             for t in range(cfg.horizon):
-                actions, _, _ = fused.act(buf, t, out=(ro.actions[t], ro.values[t], ro.log_probs[t]))
-                buf.step(t, actions)
-                fused.bootstrap(buf, t, cfg.gamma)
-                d = buf.dones[t].bool()
-                torch.where(d, e.ep_return, self._nan, out=self._ep_r[t])
-                torch.where(d, e.ep_len.float(), self._nan, out=self._ep_l[t])
-            fused.values(buf, cfg.horizon, out=self._last_values)
-            ro.compute_returns_and_advantage(self._last_values, cfg.gamma, cfg.gae_lambda)
+                self._fused_step(t)
+            self._fused_finish()
             e.join()                       # the graph is self-contained: the last epoch's refill ends inside it
             g.capture_end()
         torch.cuda.synchronize(e.device)
         e.calls = calls
         return g
 
-    def _collect_graph(self):
-        """collect() with cfg.graph_collect: sync the weights in place, replay the block's graph, read the episode
-        statistics once."""
-        e, cfg, ro, fused = self.engine, self.cfg, self.rollout, self.fused
+    def _collect_fused(self, callback):
+        """collect() with cfg.fused_act: sync the weights in place, then every step's body -- one by one, with the
+        callback's say after each, or as one replay of the block's graph -- and one read of the episode statistics."""
+        e, cfg, ro = self.engine, self.cfg, self.rollout
         buf = ro.buf
-        if e.ring_depth > 0 and e.calls % e.refill_every:
-            raise ValueError("graph_collect: a rollout must start on a refill-epoch boundary (engine.calls = %d, "
-                             "refill_every = %d)" % (e.calls, e.refill_every))
-        fused.sync()                       # eager and in place: the graphs read the new weights
+        if self.graphs is not None:
+            if callback is not None:
+                raise ValueError("graph_collect: a callback needs a host decision every step")
+            if e.ring_depth > 0 and e.calls % e.refill_every:
+                raise ValueError("graph_collect: a rollout must start on a refill-epoch boundary (engine.calls = %d, "
+                                 "refill_every = %d)" % (e.calls, e.refill_every))
+        self.fused.sync()                  # the optimiser phase since the last rollout changed the weights
+        self.fused.index_table(buf)        # act / values over all envs index by a view: no launch, nothing allocated
         if self._n_rollouts:
             buf.carry_over()               # the block advance (ring: no device work)
         self._n_rollouts += 1
         self.policy.train(False)
-        g = self.graphs.get(buf.block)
-        if g is None:
-            g = self.graphs[buf.block] = self._capture()
-        g.replay()
-        e.calls += cfg.horizon             # what the replayed buf.step calls would have counted
-        self.num_timesteps += cfg.horizon * e.n
+        if self.graphs is not None:
+            g = self.graphs.get(buf.block)
+            if g is None:
+                g = self.graphs[buf.block] = self._capture()
+            g.replay()
+            e.calls += cfg.horizon         # what the replayed buf.step calls would have counted
+            self.num_timesteps += cfg.horizon * e.n
+        else:
+            for t in range(cfg.horizon):
+                self._fused_step(t)
+                self.num_timesteps += e.n
+                if callback is not None:
+                    if callback.on_step(self.policy, self.num_timesteps) is False:
+                        self.stopped = True
+                        return None
+                    self.policy.train(False)
+            self._fused_finish()
         m = ~torch.isnan(self._ep_r)
         self.ep_returns, self.ep_lens = self._ep_r[m], self._ep_l[m]
         return ro
@@ -412,16 +425,13 @@ class Trainer:
 
     def __init__(self, policy, cfg, group=None):
         self.policy, self.cfg, self.group = policy, cfg, group
-        if getattr(cfg, "graph_train", False) and group is not None:
-            raise ValueError("graph_train does not support a data-parallel group (the all-reduce is not captured)")
+        check_group(cfg, group)
         self.lr_schedule = linear_schedule(cfg.initial_learning_rate, cfg.final_learning_rate)
         self.gen = torch.Generator(device=next(policy.parameters()).device)
         self.gen.manual_seed(cfg.seed)
         self.world = torch.distributed.get_world_size(group) if group is not None else 1
         self.fused = None              # FusedEvaluator of the rollout's engine (cfg.fused_train), made on first use
         self.update = None             # FusedUpdate of the rollout's engine (cfg.fused_update), made on first use
-        if getattr(cfg, "fused_train", False) and cfg.layout != "compact":
-            raise ValueError("fused_train needs layout='compact'")
 
     def global_adv_stats(self, buf):
         s = buf.adv_stats.clone()
@@ -456,14 +466,14 @@ class Trainer:
         if cfg.adv_norm == "global":
             g_mean, g_std, _ = self.global_adv_stats(buf)
         n = buf.T * buf.N
-        if getattr(cfg, "fused_update", False):
+        if cfg.fused_update:
             return self._train_fused_update(buf, lr, g_mean, g_std, perm_fn)
         stats = dict(pg=[], vf=[], ent=[], kl=[], clipfrac=[])
         fused = None
-        if getattr(cfg, "fused_train", False):
+        if cfg.fused_train:
             if self.fused is None or self.fused.engine is not buf.buf.engine:
                 from .fused_train import FusedEvaluator
-                self.fused = FusedEvaluator(pol, buf.buf.engine, fused_mission=getattr(cfg, "fused_mission", False))
+                self.fused = FusedEvaluator(pol, buf.buf.engine, fused_mission=cfg.fused_mission)
             fused = self.fused
             fused.prepare(buf.buf)         # the mission ids of this rollout: the table rows each minibatch computes
         for epoch in range(cfg.n_epochs):
@@ -519,7 +529,7 @@ class Trainer:
             mode, adv_stats = 2, torch.stack([g_mean, g_std]).float()
         rows = []
         graph = None
-        if getattr(cfg, "graph_train", False):          # one captured graph per epoch
+        if cfg.graph_train:                             # one captured graph per epoch
             graph = up.graph_begin(buf.buf, rollout, cfg, lr, T * N, adv_mode=mode, adv_stats=adv_stats)
         for epoch in range(cfg.n_epochs):
             perm = perm_fn(T * N) if perm_fn else torch.randperm(T * N, generator=self.gen, device=self.gen.device)
@@ -563,10 +573,9 @@ def learn(cfg, total_timesteps, device="cuda", group=None, rank=0, log=None, cal
     cfg.seed + seed_offset; the learning-rate schedule continues from `timesteps`."""
     from .policy import ActorCriticPolicy
     init = init or {}
-    if getattr(cfg, "graph_train", False) and group is not None:
-        raise ValueError("graph_train does not support a data-parallel group (the all-reduce is not captured)")
+    check_group(cfg, group)            # before anything touches the device
     torch.manual_seed(cfg.seed + rank + init.get("seed_offset", 0))
-    graph = dict(refill_every=graph_refill_every(cfg.horizon)) if getattr(cfg, "graph_collect", False) else {}
+    graph = dict(refill_every=graph_refill_every(cfg.horizon)) if cfg.graph_collect else {}
     eng = MgxEngine(n_envs=cfg.n_envs, seed=cfg.seed + init.get("seed_offset", 0), env_index_offset=rank * cfg.n_envs,
                     n_stack=cfg.n_frames_stack, terminal_mode="truncated", mission_dtype=torch.uint8,
                     device=device, reward64=True, **graph, **cfg.env)

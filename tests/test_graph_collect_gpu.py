@@ -257,6 +257,79 @@ def test_graph_collect_equals_eager_collect():
     cg.engine.poll_error()
 
 
+def _collect_before_the_shared_body(col, first):
+    """The eager fused_act collect as it stood before the collector had one per-step body, on `col`'s engine, rollout
+    and FusedActor: fresh act outputs copied into the rollout arrays, the truncation bootstrap through nonzero() +
+    values(terminal=True, envs=boot) + index_put_, the episode statistics through lists of torch.where.  Returns
+    (ep_returns, ep_lens, bootstraps)."""
+    e, cfg, ro, fused = col.engine, col.cfg, col.rollout, col.fused
+    buf = ro.buf
+    fused.sync()
+    if not first:
+        buf.carry_over()
+    col.policy.train(False)
+    gamma32 = torch.tensor(cfg.gamma, dtype=torch.float32)
+    ep_r, ep_l, boots = [], [], 0
+    for t in range(cfg.horizon):
+        actions, values, log_probs = fused.act(buf, t)
+        buf.step(t, actions)
+        boot = (buf.truncated[t].bool() & ~buf.terminated[t].bool()).nonzero().flatten()
+        if boot.numel():
+            boots += int(boot.numel())
+            tv = fused.values(buf, t, terminal=True, envs=boot)
+            r = buf.rewards[t]
+            r.index_put_((boot,), r.index_select(0, boot) + gamma32.to(tv.device) * tv)
+        ro.actions[t].copy_(actions)
+        ro.values[t].copy_(values)
+        ro.log_probs[t].copy_(log_probs)
+        d = buf.dones[t].bool()
+        ep_r.append(torch.where(d, e.ep_return, torch.nan))
+        ep_l.append(torch.where(d, e.ep_len.float(), torch.nan))
+    last_values = fused.values(buf, cfg.horizon)
+    ro.compute_returns_and_advantage(last_values, cfg.gamma, cfg.gae_lambda)
+    r, l = torch.stack(ep_r), torch.stack(ep_l)
+    m = ~torch.isnan(r)
+    return r[m], l[m], boots
+
+
+def test_eager_collect_equals_the_sequence_before_the_shared_body():
+    """collect() with fused_act on and graph_collect off, pinned to the arithmetic of the eager loop it replaced.
+    n_stack 4, horizon 72: the truncations of step 64 fall into the first rollout, those of step 128 into the second,
+    which also crosses the ring-block advance; the weights change in between.  Actions, values, log-probs, rewards,
+    dones, advantages, returns, adv_stats and the episode statistics are equal bit for bit after each rollout."""
+    _gpu()
+    # `ref` only lends its engine, rollout and FusedActor: its collect() is never called, so that its config has
+    # graph_collect on (a capture stream, the horizon checked against refill_every = 8) plays no part
+    ce, ref = _collectors(4, 72, 8)
+    ce.start()
+    ref.start()
+    boots = 0
+    for i in range(2):
+        if i:
+            _perturb(ce, ref, i)
+        got = ce.collect()
+        ep_r, ep_l, n = _collect_before_the_shared_body(ref, first=(i == 0))
+        boots += n
+        want = ref.rollout
+        assert n == int((got.buf.truncated.bool() & ~got.buf.terminated.bool()).sum()), i
+        for name in ("actions", "values", "log_probs", "advantages", "returns", "adv_stats"):
+            a, b = getattr(got, name), getattr(want, name)
+            assert a.shape == b.shape and torch.equal(a, b), (i, name)
+            if a.dtype == torch.float32:
+                assert torch.equal(_bits(a), _bits(b)), (i, name)
+        assert torch.equal(_bits(got.buf.rewards), _bits(want.buf.rewards)), (i, "rewards")
+        for name in ("terminated", "truncated", "dones"):
+            assert torch.equal(getattr(got.buf, name), getattr(want.buf, name)), (i, name)
+        assert ce.ep_returns.numel() > 0 and ce.ep_returns.shape == ep_r.shape, i
+        assert torch.equal(_bits(ce.ep_returns), _bits(ep_r)), (i, "ep_returns")
+        assert torch.equal(_bits(ce.ep_lens), _bits(ep_l)), (i, "ep_lens")
+        assert torch.equal(ce.fused.counter, ref.fused.counter), (i, "sampling counter")
+    assert boots > 0, "no truncation bootstrap exercised"
+    assert ce.num_timesteps == 2 * 72 * N_ENVS
+    ce.engine.poll_error()
+    ref.engine.poll_error()
+
+
 def test_graph_collect_three_ring_blocks():
     """n_stack 8, horizon 4, refill_every 4: three ring blocks, 18 rollouts."""
     _gpu()

@@ -277,6 +277,102 @@ def test_trainer_graph_equals_eager(variant):
     col.engine.poll_error()
 
 
+PIN_SIZES = (48, 32, 1)                # one tile each (see the module docstring); one sample takes adv_mode 0
+PIN_LRS = (3e-4, 1.1e-4, 3e-6)
+
+
+def _sequence_before_the_shared_body(pol, eng, buf, cfg):
+    """The eager minibatch step as it stood before FusedUpdate had one body, from the public raw calls:
+    forward_raw + index_copy_ into a zeroed table, the policy forward with fresh logits / values, ppo_loss, the policy
+    backward, index_select + backward_raw, adam_step by value.  Returns (arena, total_norm, step(index, sel, rollout,
+    lr, adv_mode) -> statistics row)."""
+    from mgx import _lib
+    from mgx.fused_train import FusedEvaluator
+    from mgx.fused_update import ParamArena, adam_step, ppo_loss
+    L = _lib.load()
+    ev = FusedEvaluator(pol, eng, fused_mission=True)
+    enc, k = ev.mission, ev.K
+    a = ParamArena(pol)
+    ev.prepare(buf)
+    f32 = dict(dtype=torch.float32, device=eng.device)
+    table, g_table = torch.zeros((256 * k, 128), **f32), torch.empty((256, k, 128), **f32)
+    norm = torch.zeros(1, **f32)
+    loss_scratch = torch.empty(int(L.mgx_ppo_loss_scratch_words(1 << 30)), **f32)
+    adam_scratch = torch.empty(int(L.mgx_adam_scratch_words(a.words)), **f32)
+    blob, g_blob = a.param[:a.blob_words], a.grad[:a.blob_words]
+    mission, g_mission = tuple(a.views(a.param, slice(20, 25))), tuple(a.views(a.grad, slice(20, 25)))
+    stacks, rows = ev._stacks, ev._rows
+    ws = torch.empty(int(L.mgx_mission_workspace_words(stacks.shape[0], stacks.shape[1])), **f32)
+    pg = pol.optimizer.param_groups[0]
+
+    def step(index, sel, rollout, lr, adv_mode):
+        stats = torch.zeros(8, **f32)
+        table.index_copy_(0, rows, enc.forward_raw(stacks, mission, ws))
+        logits, values = ev.forward_raw(buf, index, blob, table)
+        g_logits, g_values, _ = ppo_loss(logits, values, *rollout, cfg.clip_range, cfg.clip_range_vf, cfg.ent_coef,
+                                         cfg.vf_coef, adv_mode=adv_mode, sel=sel, scratch=loss_scratch,
+                                         out=(torch.empty_like(logits), torch.empty_like(values), stats))
+        ev.backward_raw(buf, index, blob, table, g_logits, g_values, out=(g_blob, g_table))
+        g_feat = g_table.view(-1, 128).index_select(0, rows)
+        enc.backward_raw(stacks, mission, g_feat, ws, out=g_mission)
+        a.step += 1
+        adam_step(a.param, a.grad, a.exp_avg, a.exp_avg_sq, lr, a.step, betas=pg["betas"], eps=pg["eps"],
+                  max_grad_norm=cfg.max_grad_norm, grad_scale=1.0, total_norm=norm, scratch=adam_scratch)
+        return stats
+
+    return a, norm, step
+
+
+@pytest.mark.parametrize("k", [4, 1])
+def test_step_equals_the_sequence_before_the_shared_body(k):
+    """FusedUpdate.step pinned to the arithmetic of the eager step it replaced.  One collected rollout of 8 envs x 16
+    steps; two policies of the same weights, each with its own arena; minibatches of 48, 32 and 1 sample of one
+    permutation at three learning rates, stepped one after another (twice over: the per-size buffers are reused).
+    After every step all 25 parameters, both moments, the gradient arena, total_norm and the statistics row are equal
+    bit for bit."""
+    _gpu()
+    from mgx.fused_update import FusedUpdate
+    from mgx.policy import ActorCriticPolicy
+    cfg = _cfg(k, False)
+    col, tr = _leg(cfg)
+    ro = col.collect()
+    pol_a = tr.policy
+    torch.manual_seed(0)                            # _leg's policy seed
+    pol_b = ActorCriticPolicy(n_stack=k).cuda()
+    start = [p.detach().clone() for p in pol_a.parameters()]
+    assert len(start) == 25 and all(_same(x, y) for x, y in zip(start, pol_b.parameters()))
+    up = FusedUpdate(pol_a, col.engine)
+    up.prepare(ro.buf)
+    ref, ref_norm, ref_step = _sequence_before_the_shared_body(pol_b, col.engine, ro.buf, cfg)
+    T, N = ro.T, ro.N
+    perm = torch.randperm(T * N, device="cuda", generator=torch.Generator(device="cuda").manual_seed(9))
+    env, t = perm // T, perm % T
+    index = ro.buf.index(t, env).to(torch.int64).contiguous()
+    sel = (t * N + env).contiguous()
+    rollout = (ro.actions, ro.values, ro.log_probs, ro.advantages, ro.returns)
+    s = 0
+    for i, m in enumerate(PIN_SIZES * 2):
+        if i == 3:
+            s = 10                                  # the second pass: other samples of the 128
+        assert s + m <= T * N
+        lr, mode = PIN_LRS[i % 3], 1 if m > 1 else 0
+        got = torch.zeros(8, device="cuda")
+        up.step(ro.buf, index[s:s + m], sel[s:s + m], rollout, cfg, lr, got, adv_mode=mode)
+        want = ref_step(index[s:s + m], sel[s:s + m], rollout, lr, mode)
+        torch.cuda.synchronize()
+        tag = (k, i, m)
+        assert up.arena.step == ref.step == i + 1, tag
+        assert _same(got, want) and bool(torch.isfinite(got[:6]).all()), (tag, got.tolist(), want.tolist())
+        for j, (x, y) in enumerate(zip(pol_a.parameters(), pol_b.parameters())):
+            assert _same(x, y), (tag, "parameter", j)
+        for name in ("param", "grad", "exp_avg", "exp_avg_sq"):
+            assert _same(getattr(up.arena, name), getattr(ref, name)), (tag, name)
+        assert _same(up.total_norm, ref_norm) and float(ref_norm) > 0, tag
+        s += m
+    assert not any(_same(x, y) for x, y in zip(pol_a.parameters(), start))
+    col.engine.poll_error()
+
+
 def test_hand_back_to_eager():
     """Two graph rounds, then one round with graph_train off on the same trainer (its generator goes on): equal to
     three all-eager rounds."""

@@ -7,7 +7,8 @@ it replaces, the eager fused_act collect of the same build.
              alternating repeats after a warm-up that captures every block's graph; at two shapes: config 3's (65,536
              envs, horizon 16, n_stack 4, multi / 'pick up' / 8x8 / 4 objects) and the reference recipe's (16 envs,
              horizon 1024)
-  bootstrap  FusedActor.bootstrap alone against the eager nonzero() + values + index_put_ sequence on one step of a
+  bootstrap  FusedActor.bootstrap alone against the nonzero() + values + index_put_ sequence it replaced (the torch
+             policy's collect still runs that sequence; both fused collects run the kernel) on one step of a
              65,536-env buffer with 1/64 of the envs truncated, and both with no env truncated (what every step pays)
 Device events and host wall time (a collect ends with its one host read, so the wall time is the whole rollout);
 median and range (min, max).

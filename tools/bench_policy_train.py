@@ -368,15 +368,14 @@ def part_update_step(args):
     a, enc = up.arena, up.ev.mission
     stacks, trows = up.ev._stacks, up.ev._rows
     ws = enc._workspace(stacks.shape[0], stacks.shape[1])
-    logits, values = up.ev.forward_raw(ro.buf, index, up._blob, up.table)
-    g_logits, g_values = torch.empty_like(logits), torch.empty_like(values)
+    logits, values, g_logits, g_values = up._buffers(rows)           # the step's own per-size buffers
     state = dict(step=a.step)
 
     def mission_forward():
-        up.table.index_copy_(0, trows, enc.forward_raw(stacks, up._mission, ws))
+        enc.forward_rows(stacks, up._mission, up.table, trows, ws)
 
     def mission_backward():
-        enc.backward_raw(stacks, up._mission, up.g_table.view(-1, 128).index_select(0, trows), ws, out=up._g_mission)
+        enc.backward_rows(stacks, up._mission, up.g_table.view(-1, 128), trows, ws, out=up._g_mission)
 
     def adam():
         state["step"] += 1
@@ -538,8 +537,7 @@ def part_graph_pieces(args):
     b, enc, ev = up._gbuf, up.ev.mission, up.ev
     _, stacks, rows, ws = next(iter(up._graphs.values()))
     index, sel = b["index"][:m], b["sel"][:m]
-    logits, values = b["logits"][:m], b["values"][:m]
-    g_logits, g_values = up._batch[m]
+    logits, values, g_logits, g_values = up._buffers(m)
     rollout = (ro.actions, ro.values, ro.log_probs, ro.advantages, ro.returns)
     a, pg = up.arena, tr.policy.optimizer.param_groups[0]
     b["cursor"].zero_()                                              # 256 entries: enough for every call below
