@@ -558,6 +558,43 @@ mgx_status mgx_adam_step_sched(float *param_dev, float *grad_dev, float *exp_avg
                                int32_t table_len, int32_t *cursor_dev, float *total_norm_dev, float *scratch_dev,
                                int64_t scratch_words, void *stream);
 
+/* ---- Evaluation records on the device (added within ABI 9) -------------------------------------------
+ * SB3 evaluate_policy's per-step episode accounting (stable_baselines3/common/evaluation.py; the loop body of
+ * mgx/evaluation.py evaluate_policy) for every env of ONE vector step, in one launch and with no host decision,
+ * so a captured graph can hold a block of evaluation steps (mgx/evaluation.py GraphEvaluator).
+ * For env e, with target = (n_eval_episodes + e) / n_envs in integer arithmetic (episode_count_targets), the
+ * step index t = base_dev[0] + step_offset and c = counts_dev[e]:
+ *    rec = done[e] != 0 && c < target
+ *    if rec: rewards[e][c] = reward64[e] (or (double) ep_return[e]),  lengths[e][c] = ep_len[e],
+ *            when[e][c] = t,  missions[e][c] = mission_id[e],  counts[e] = c + 1
+ *    remaining_dev[0] -= the number of envs with rec, one integer atomic per workgroup of 64 envs that recorded
+ *    anything (a ballot's popcount); no float atomics, every output is reproducible.
+ * Slots at or beyond an env's count and envs that record nothing are NOT written.  base_dev is only read: a
+ * captured block of K steps bakes step_offset = 0 .. K-1 into its launches and advances base_dev by K once at
+ * its end, so no launch orders against another through the counter.  The host sets remaining_dev to the sum of
+ * the targets (= n_eval_episodes) before the first step; the evaluation is over when it reads 0.  A count
+ * outside [0, cap) records nothing (the tables are never written out of bounds). */
+typedef struct mgx_eval_record_args {
+    const uint8_t *done_dev;        /* u8 [n_envs]: this step's done flags */
+    const double *reward64_dev;     /* f64 [n_envs]: this step's reward (only an episode's last step pays, so it */
+    const float *ep_return_dev;     /*   is the Monitor sum), or NULL: f32 [n_envs] ep_return_dev is read instead */
+    const int32_t *ep_len_dev;      /* i32 [n_envs]: the length of the episode that just ended */
+    const uint8_t *mission_id_dev;  /* u8 [n_envs]: the mission id of the observation the action was taken on */
+    const int64_t *base_dev;        /* i64 [1]: step index of step_offset 0; READ only */
+    int32_t *counts_dev;            /* i32 [n_envs]: episodes recorded so far; updated in place */
+    double *rewards_dev;            /* f64 [n_envs][cap] */
+    int32_t *lengths_dev;           /* i32 [n_envs][cap] */
+    int64_t *when_dev;              /* i64 [n_envs][cap] */
+    uint8_t *missions_dev;          /* u8 [n_envs][cap] */
+    int32_t *remaining_dev;         /* i32 [1]: episodes still owed */
+} mgx_eval_record_args;
+
+/* Takes no engine handle.  Only enqueues on `stream` (no allocation, no host sync; capturable).
+ * MGX_ERR_INVALID before any HIP call for: a null pointer (one of reward64_dev / ep_return_dev may be null),
+ * n_envs <= 0, n_eval_episodes < 0, cap < 1, cap below the largest target ceil(n_eval_episodes / n_envs). */
+mgx_status mgx_eval_record(int64_t n_envs, int64_t n_eval_episodes, int64_t cap, int64_t step_offset,
+                           const mgx_eval_record_args *a, void *stream);
+
 /* Makes `stream` wait for the in-flight refill, if any (no host sync). */
 mgx_status mgx_join(mgx_handle *h, void *stream);
 

@@ -2739,6 +2739,7 @@ __global__ __launch_bounds__(256) void mgx_gather_kernel(const uint8_t *__restri
 #include "mgx_policy_grad.h"   // mgx_policy_backward's kernels (its gradient)
 #include "mgx_mission.h"   // mgx_mission_forward / mgx_mission_backward: the mission Embedding + GRU
 #include "mgx_update.h"    // mgx_ppo_loss / mgx_adam_step: the PPO loss and the clip + Adam step
+#include "mgx_eval.h"      // mgx_eval_record: evaluate_policy's per-step episode accounting
 
 // ================================================================== host side
 thread_local std::string g_last_error;
@@ -4197,6 +4198,30 @@ mgx_status mgx_adam_step_sched(float *param_dev, float *grad_dev, float *exp_avg
     if (table_len < 1) return fail(MGX_ERR_INVALID, "mgx_adam_step_sched: table_len must be positive");
     return adam_step("mgx_adam_step_sched", param_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, n_words, p, table_dev,
                      table_len, cursor_dev, total_norm_dev, scratch_dev, scratch_words, stream);
+}
+
+// ---- evaluation records (mgx_eval.h): no engine handle
+mgx_status mgx_eval_record(int64_t n_envs, int64_t n_eval_episodes, int64_t cap, int64_t step_offset,
+                           const mgx_eval_record_args *p, void *stream) {
+    if (!p || !p->done_dev || (!p->reward64_dev && !p->ep_return_dev) || !p->ep_len_dev || !p->mission_id_dev ||
+        !p->base_dev || !p->counts_dev || !p->rewards_dev || !p->lengths_dev || !p->when_dev || !p->missions_dev ||
+        !p->remaining_dev)
+        return fail(MGX_ERR_INVALID, "mgx_eval_record: null pointer");
+    if (n_envs <= 0) return fail(MGX_ERR_INVALID, "mgx_eval_record: n_envs must be > 0");
+    if (n_envs > (int64_t)INT32_MAX * EVAL_THREADS) return fail(MGX_ERR_INVALID, "mgx_eval_record: n_envs too large");
+    if (n_eval_episodes < 0) return fail(MGX_ERR_INVALID, "mgx_eval_record: n_eval_episodes must be >= 0");
+    if (cap < 1) return fail(MGX_ERR_INVALID, "mgx_eval_record: cap must be >= 1");
+    if (cap < n_eval_episodes / n_envs + (n_eval_episodes % n_envs != 0))      // the largest target
+        return fail(MGX_ERR_INVALID, "mgx_eval_record: cap below ceil(n_eval_episodes / n_envs)");
+    EvalRecordArgs a;
+    a.done = p->done_dev; a.reward64 = p->reward64_dev; a.ep_return = p->ep_return_dev; a.ep_len = p->ep_len_dev;
+    a.mission_id = p->mission_id_dev; a.base = p->base_dev; a.counts = p->counts_dev; a.rewards = p->rewards_dev;
+    a.lengths = p->lengths_dev; a.when = p->when_dev; a.missions = p->missions_dev; a.remaining = p->remaining_dev;
+    a.n = n_envs; a.n_eval = n_eval_episodes; a.cap = cap; a.step_offset = step_offset;
+    const int64_t groups = (n_envs + EVAL_THREADS - 1) / EVAL_THREADS;
+    hipLaunchKernelGGL(mgx_eval_record_kernel, dim3((unsigned)groups), dim3(EVAL_THREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return MGX_OK;
 }
 
 mgx_status mgx_gae(const float *rewards_dev, const float *values_dev, const float *episode_starts_dev,

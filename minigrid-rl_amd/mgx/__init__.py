@@ -6,7 +6,8 @@ src/custom_env.py, src/environment.py, src/ppo.py) over libmgx.so (HIP/gfx950).
 from ._lib import MgxError, mission_text  # noqa: F401
 from .describe import LLMDescriptionWrapper  # noqa: F401
 from .engine import MgxEngine, gae, gae_dones, random_actions  # noqa: F401
-from .evaluation import EvalCallback, StopTrainingOnRewardThreshold, evaluate_policy, evaluate_test_protocol  # noqa: F401
+from .evaluation import (EvalCallback, GraphEvaluator, StopTrainingOnRewardThreshold, evaluate_policy,  # noqa: F401
+                         evaluate_test_protocol, summarize_missions)
 from .vec_env import MgxVecEnv  # noqa: F401
 
-__all__ = ["EvalCallback", "LLMDescriptionWrapper", "MgxEngine", "MgxError", "MgxVecEnv", "StopTrainingOnRewardThreshold", "evaluate_policy", "evaluate_test_protocol", "gae", "gae_dones", "mission_text", "random_actions"]
+__all__ = ["EvalCallback", "GraphEvaluator", "LLMDescriptionWrapper", "MgxEngine", "MgxError", "MgxVecEnv", "StopTrainingOnRewardThreshold", "evaluate_policy", "evaluate_test_protocol", "gae", "gae_dones", "mission_text", "random_actions", "summarize_missions"]

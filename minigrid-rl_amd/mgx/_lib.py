@@ -31,7 +31,8 @@ EXPORTS = ("mgx_last_error", "mgx_abi_version", "mgx_create", "mgx_destroy", "mg
            "mgx_policy_act", "mgx_policy_bootstrap", "mgx_policy_grad_scratch_words", "mgx_policy_backward",
            "mgx_mission_workspace_words", "mgx_mission_forward", "mgx_mission_backward",
            "mgx_ppo_loss_scratch_words", "mgx_ppo_loss", "mgx_adam_scratch_words", "mgx_adam_step",
-           "mgx_mission_forward_rows", "mgx_mission_backward_rows", "mgx_adam_schedule", "mgx_adam_step_sched")
+           "mgx_mission_forward_rows", "mgx_mission_backward_rows", "mgx_adam_schedule", "mgx_adam_step_sched",
+           "mgx_eval_record")
 CLOCK_CLASSES = 4   # == MGX_CLOCK_CLASSES (include/mgx.h)
 
 
@@ -151,6 +152,15 @@ class MgxAdamSched(ctypes.Structure):
     _fields_ = [("step_size", ctypes.c_float), ("bc2_sqrt", ctypes.c_float)]
 
 
+class MgxEvalRecordArgs(ctypes.Structure):
+    _fields_ = [
+        ("done_dev", ctypes.c_void_p), ("reward64_dev", ctypes.c_void_p), ("ep_return_dev", ctypes.c_void_p),
+        ("ep_len_dev", ctypes.c_void_p), ("mission_id_dev", ctypes.c_void_p), ("base_dev", ctypes.c_void_p),
+        ("counts_dev", ctypes.c_void_p), ("rewards_dev", ctypes.c_void_p), ("lengths_dev", ctypes.c_void_p),
+        ("when_dev", ctypes.c_void_p), ("missions_dev", ctypes.c_void_p), ("remaining_dev", ctypes.c_void_p),
+    ]
+
+
 class MgxError(RuntimeError):
     pass
 
@@ -218,6 +228,7 @@ def load():
     L.mgx_adam_schedule.argtypes = [ctypes.POINTER(MgxAdamArgs), ctypes.POINTER(ctypes.c_double), I64, ctypes.c_int32,
                                     ctypes.POINTER(MgxAdamSched)]
     L.mgx_adam_step_sched.argtypes = [P, P, P, P, I64, ctypes.POINTER(MgxAdamArgs), P, ctypes.c_int32, P, P, P, I64, P]
+    L.mgx_eval_record.argtypes = [I64, I64, I64, I64, ctypes.POINTER(MgxEvalRecordArgs), P]
     L.mgx_set_clock.argtypes = [P, P, I, ctypes.POINTER(I)]
     L.mgx_clock_words.argtypes = [P, I]
     L.mgx_clock_words.restype = I64

@@ -113,6 +113,26 @@ def check_group(cfg, group):
         raise ValueError("graph_train does not support a data-parallel group (the all-reduce is not captured)")
 
 
+def check_graph_callback(callback):
+    """graph_collect replays a whole rollout: only a callback that allows being called after it is accepted."""
+    if callback is not None and not getattr(callback, "deferrable", False):
+        raise ValueError("graph_collect: a callback needs a host decision every step (only a callback whose "
+                         "`deferrable` attribute is true, such as EvalCallback, can be called after the replay)")
+
+
+def deferred_on_steps(callback, policy, num_timesteps, n_envs, horizon):
+    """The on_step calls of a rollout of `horizon` steps that started at `num_timesteps`, made after the rollout
+    (a `deferrable` callback under graph_collect): once per step, in order, each with the step's own count
+    num_timesteps + (t + 1) * n_envs.  Returns the count of the step whose call returned False (later steps are
+    not called), else None."""
+    for t in range(horizon):
+        now = num_timesteps + (t + 1) * n_envs
+        if callback.on_step(policy, now) is False:
+            return now
+        policy.train(False)
+    return None
+
+
 def minibatch_env_t(perm, batch_size, T):
     """(env, t) of every minibatch of `perm`, a permutation of the env-major flat index i = env * T + t (SB3
     swap_and_flatten), in slices of batch_size; the last one may be shorter."""
@@ -383,12 +403,12 @@ class CompactRolloutCollector:
 
     def _collect_fused(self, callback):
         """collect() with cfg.fused_act: sync the weights in place, then every step's body -- one by one, with the
-        callback's say after each, or as one replay of the block's graph -- and one read of the episode statistics."""
+        callback's say after each, or as one replay of the block's graph, a deferrable callback's steps after it
+         -- and one read of the episode statistics."""
         e, cfg, ro = self.engine, self.cfg, self.rollout
         buf = ro.buf
         if self.graphs is not None:
-            if callback is not None:
-                raise ValueError("graph_collect: a callback needs a host decision every step")
+            check_graph_callback(callback)
             if e.ring_depth > 0 and e.calls % e.refill_every:
                 raise ValueError("graph_collect: a rollout must start on a refill-epoch boundary (engine.calls = %d, "
                                  "refill_every = %d)" % (e.calls, e.refill_every))
@@ -404,7 +424,14 @@ class CompactRolloutCollector:
                 g = self.graphs[buf.block] = self._capture()
             g.replay()
             e.calls += cfg.horizon         # what the replayed buf.step calls would have counted
+            before = self.num_timesteps
             self.num_timesteps += cfg.horizon * e.n
+            if callback is not None:       # the weights were constant over the rollout: every step's call, now
+                at = deferred_on_steps(callback, self.policy, before, e.n, cfg.horizon)
+                if at is not None:
+                    self.stopped = True
+                    self.num_timesteps = at
+                    return None
         else:
             for t in range(cfg.horizon):
                 self._fused_step(t)
@@ -608,7 +635,13 @@ def learn(cfg, total_timesteps, device="cuda", group=None, rank=0, log=None, cal
             log(st)
     if evaluate:
         from .evaluation import evaluate_policy
-        mean_r, std_r = evaluate_policy(pol, eng, cfg.n_eval_episodes)
+        # cfg.fused_act: through the collector's FusedActor; with cfg.graph_collect as captured blocks as well (the
+        # training engine's refill epoch already divides them; GraphEvaluator syncs the actor itself)
+        fused = getattr(col, "fused", None)
+        graph = True if fused is not None and cfg.graph_collect else None
+        if fused is not None and graph is None:
+            fused.sync()                               # the last optimiser phase changed the weights
+        mean_r, std_r = evaluate_policy(pol, eng, cfg.n_eval_episodes, fused=fused, graph=graph)
         if hist:
             hist[-1].update(mean_reward=mean_r, std_reward=std_r)
         if log:
