@@ -564,69 +564,76 @@ __device__ __forceinline__ uint32_t guard10(uint64_t acc) {
 // rejected cell back to want x.  Its state (need_c, have_x with the latched x, the rejection count) is carried
 // from one ten-word pass to the next, so a draw that crosses the window's end continues in the next pass: a pass
 // consumes the words through the accepted cell's y, or all ten (the pending draw rejected every word left).
+// cell_pass is ONE such pass with one way out (round 18): it returns whether the cell (x, y) was accepted; a pass
+// that would need a word past the cap, or whose probe finds no acceptable cell, abandons the attempt instead
+// (G.abort, the cursor at the cap) and consumes nothing.  Cap, probe and consumption are selects, not exits, so a
+// loop around it carries the stream's registers through a single back edge.
+template <int NW, typename Bad, typename Sat>
+__device__ __forceinline__ bool cell_pass(Gen<NW> &G, const RbConst KX, const RbConst KY, int x0, int y0, int &x, int &y,
+                                          Bad bad, Sat sat /* probe after SAT_PROBE rejections; null: none */,
+                                          const RbConst KC, int &choice, bool &need_c, bool &have_x, uint32_t &xv,
+                                          int &rej) {
+    constexpr uint64_t GM = 32ull * MT_REP;              // guard bit of every slot
+    GCOUNT(G, 27);
+    GCOUNT(G, 21);
+    const int o6 = (int)__umul24((uint32_t)G.go, 6u);
+    const uint64_t f = ((G.ga >> o6) | (G.gb << (60 - o6))) & MT_LOW60;   // words cur..cur+9
+    uint32_t avail = 0x3FFu;                             // slots not consumed by an earlier draw
+    if (need_c) {                                        // no accepted word: the choice takes all ten (avail = 0)
+        const uint32_t mc = guard10((KC.c1 - f) & GM);
+        const uint32_t j = (uint32_t)__builtin_ctz(mc | 0x400u);
+        choice = mc ? (int)((((uint32_t)(f >> (6u * j))) & 31u) >> KC.sh) : choice;
+        avail &= ~1u << j;
+        need_c = mc == 0u;
+    }
+    const uint32_t mx = guard10((KX.c1 - f) & GM), my = guard10((KY.c1 - f) & GM);   // slot passes x's / y's test
+    // one candidate cell per iteration: the cell is accepted, or x or y runs past these ten words (slot 10 = none:
+    // the shifted masks then empty `avail`), or the probe finds the placement unsatisfiable
+    bool ok, dead = false;
+    uint32_t jy;
+#pragma unroll 1
+    for (;;) {
+        GCOUNT(G, 25);
+        const uint32_t cx = mx & avail;
+        const uint32_t jx = (uint32_t)__builtin_ctz(cx | 0x400u);
+        const uint32_t xn = (((uint32_t)(f >> (6u * jx))) & 31u) >> KX.sh;
+        const uint32_t av = have_x ? avail : avail & (~1u << jx);
+        xv = have_x ? xv : xn;
+        const uint32_t cy = my & av;
+        jy = (uint32_t)__builtin_ctz(cy | 0x400u);
+        x = x0 + (int)xv;
+        y = y0 + (int)((((uint32_t)(f >> (6u * jy))) & 31u) >> KY.sh);
+        avail = av & (~1u << jy);
+        have_x = cy == 0u && (have_x || cx != 0u);   // an x without its y stays latched
+        ok = cy != 0u && !bad(x, y);
+        if (ok || cy == 0u) break;
+        if (++rej == SAT_PROBE && !sat()) { dead = true; break; }
+    }
+    const int used = ok ? (int)jy + 1 : MT_FIELDS;
+    const uint32_t left = G.llw - (uint32_t)(G.cur - G.astart);
+    const bool stop = dead || (uint32_t)used > left;     // unsatisfiable, or a draw would pass the cap
+    const int adv = stop ? 0 : used;
+    G.cur = stop ? G.astart + G.llw : G.cur + (uint64_t)used;
+    G.abort |= stop;
+    // consume: the group rotation as selects; g + 2 re-read either way (the same group when nothing rotates)
+    G.go += adv;
+    const bool rot = G.go >= MT_FIELDS;
+    G.go -= rot ? MT_FIELDS : 0;
+    G.ga = rot ? G.gb : G.ga;
+    G.gb = rot ? G.gc : G.gb;
+    G.gi += rot ? 1ull : 0ull;
+    G.gc = win_group(G, G.gi + 2);
+    return ok && !stop;
+}
+// passes until a cell is accepted or the attempt is abandoned (G.abort)
 template <int NW, typename Bad, typename Sat>
 __device__ __forceinline__ void draw_cell(Gen<NW> &G, const RbConst KX, const RbConst KY, int x0, int y0, int &x, int &y,
-                                          Bad bad, Sat sat /* probe after SAT_PROBE rejections; null: none */,
-                                          bool has_c, const RbConst KC, int &choice) {
-    constexpr uint64_t GM = 32ull * MT_REP;              // guard bit of every slot
+                                          Bad bad, Sat sat, bool has_c, const RbConst KC, int &choice) {
     int rej = 0;
     bool need_c = has_c, have_x = false;
     uint32_t xv = 0;
 #pragma unroll 1
-    for (;;) {
-        GCOUNT(G, 27);
-        GCOUNT(G, 21);
-        const int o6 = (int)__umul24((uint32_t)G.go, 6u);
-        const uint64_t f = ((G.ga >> o6) | (G.gb << (60 - o6))) & MT_LOW60;   // words cur..cur+9
-        uint32_t avail = 0x3FFu;                         // slots not consumed by an earlier draw
-        if (need_c) {                                    // no accepted word: the choice takes all ten (avail = 0)
-            const uint32_t mc = guard10((KC.c1 - f) & GM);
-            const uint32_t j = (uint32_t)__builtin_ctz(mc | 0x400u);
-            choice = mc ? (int)((((uint32_t)(f >> (6u * j))) & 31u) >> KC.sh) : choice;
-            avail &= ~1u << j;
-            need_c = mc == 0u;
-        }
-        const uint32_t mx = guard10((KX.c1 - f) & GM), my = guard10((KY.c1 - f) & GM);   // slot passes x's / y's test
-        // one candidate cell per iteration, one exit: the cell is accepted, or x or y runs past these ten words
-        // (slot 10 = none: the shifted masks then empty `avail`)
-        bool ok;
-        uint32_t jy;
-#pragma unroll 1
-        for (;;) {
-            GCOUNT(G, 25);
-            const uint32_t cx = mx & avail;
-            const uint32_t jx = (uint32_t)__builtin_ctz(cx | 0x400u);
-            const uint32_t xn = (((uint32_t)(f >> (6u * jx))) & 31u) >> KX.sh;
-            const uint32_t av = have_x ? avail : avail & (~1u << jx);
-            xv = have_x ? xv : xn;
-            const uint32_t cy = my & av;
-            jy = (uint32_t)__builtin_ctz(cy | 0x400u);
-            x = x0 + (int)xv;
-            y = y0 + (int)((((uint32_t)(f >> (6u * jy))) & 31u) >> KY.sh);
-            avail = av & (~1u << jy);
-            have_x = cy == 0u && (have_x || cx != 0u);   // an x without its y stays latched
-            ok = cy != 0u && !bad(x, y);
-            if (ok || cy == 0u) break;
-            if (++rej == SAT_PROBE && !sat()) { live_lock(G); return; }
-        }
-        const int used = ok ? (int)jy + 1 : MT_FIELDS;
-        const uint32_t left = G.llw - (uint32_t)(G.cur - G.astart);
-        if ((uint32_t)used > left) {                     // a draw would pass the cap
-            G.cur = G.astart + G.llw;
-            G.abort = true;
-            return;
-        }
-        // consume: the group rotation as selects; g + 2 re-read either way (the same group when nothing rotates)
-        G.cur += (uint64_t)used;
-        G.go += used;
-        const bool rot = G.go >= MT_FIELDS;
-        G.go -= rot ? MT_FIELDS : 0;
-        G.ga = rot ? G.gb : G.ga;
-        G.gb = rot ? G.gc : G.gb;
-        G.gi += rot ? 1ull : 0ull;
-        G.gc = win_group(G, G.gi + 2);
-        if (ok) return;
-    }
+    while (!cell_pass(G, KX, KY, x0, y0, x, y, bad, sat, KC, choice, need_c, have_x, xv, rej) && !G.abort) {}
 }
 
 template <int NW>
@@ -789,10 +796,10 @@ __device__ __forceinline__ void put_door(Gen<NW> &G, int x, int y, uint8_t code)
     if (y < S - 1) G.dn.set(b + S);
 }
 
-// Cells [x0, x1] x [y0, y1] that a placement loop would accept, as row masks of the
-// register bit sets (S <= 11): none -> the reference's `while True` never ends, so the
-// live-lock policy applies at once instead of after SAT_PROBE rejected draws (same
-// end state: the attempt's cursor jumps to its cap).  Excluded points: (-1,-1) = none.
+// Cells [x0, x0 + wx) x [y0, y0 + wy) that a placement loop would accept, as row masks of the
+// register bit set of the cells it rejects (S <= 11): none -> the reference's `while True` never
+// ends, so the live-lock policy applies at once instead of after SAT_PROBE rejected draws (same
+// end state: the attempt's cursor jumps to its cap).
 template <int NW>
 __device__ __forceinline__ uint32_t bits_row(const Bits<NW> &B, int y, int S) {
     const int b = y * S;
@@ -804,21 +811,13 @@ __device__ __forceinline__ uint32_t bits_row(const Bits<NW> &B, int y, int S) {
     return (uint32_t)v & ((1u << S) - 1u);
 }
 template <int NW>
-__device__ __forceinline__ bool rect_has_free(const Gen<NW> &G, int x0, int x1, int y0, int y1, bool use_occ,
-                                              int ax, int ay, int bx, int by, int cx, int cy) {
+__device__ __forceinline__ bool rect_has_free(const Bits<NW> &bad, int x0, int wx, int y0, int wy, int S) {
     if constexpr (NW == 4) {
         return true;                      // S > 11: the in-loop SAT_PROBE check handles it
     } else {
-        const uint32_t rowmask = ((1u << (x1 - x0 + 1)) - 1u) << x0;
+        const uint32_t rowmask = ((1u << wx) - 1u) << x0;
         bool sat = false;
-        for (int y = y0; y <= y1; y++) {
-            uint32_t bad = bits_row(G.dn, y, G.S);
-            if (use_occ) bad |= bits_row(G.occ, y, G.S);
-            if (ay == y && ax >= 0) bad |= 1u << ax;
-            if (by == y && bx >= 0) bad |= 1u << bx;
-            if (cy == y && cx >= 0) bad |= 1u << cx;
-            sat |= (rowmask & ~bad) != 0;
-        }
+        for (int y = y0; y < y0 + wy; y++) sat |= (rowmask & ~bits_row(bad, y, S)) != 0;
         return sat;
     }
 }
@@ -854,12 +853,12 @@ __device__ __forceinline__ int room_of(int nr, int x, int y, int mid) {
     return left ? (up ? 0 : 1) : (up ? 2 : 3);
 }
 
-__device__ __forceinline__ void room_rect(int nr, int r, int mid, int S, int &x0, int &x1, int &y0, int &y1) {
-    const bool left = (nr == 2) ? r == 0 : r <= 1;
-    const bool full_h = nr == 2 || (nr == 3 && r == 2);
-    const bool up = (r == 0) || (nr == 4 && r == 2);
-    x0 = left ? 1 : mid + 1; x1 = left ? mid - 1 : S - 2;
-    y0 = full_h ? 1 : (up ? 1 : mid + 1); y1 = full_h ? S - 2 : (up ? mid - 1 : S - 2);
+// Room r's interior, as classes of the middle wall's two sides: columns A = [1, mid - 1] (left) or B = [mid + 1, S - 2]
+// (right); rows A = [1, mid - 1] (upper), B = [mid + 1, S - 2] (lower) or F = [1, S - 2] (full height: both rooms of
+// the 2-room layout, the right room of the 3-room one).  Per room a nibble: bit 0 = column class B, bit 1 = rows
+// start below the wall (B), bit 2 = full height.
+__device__ __forceinline__ uint32_t room_classes(int nr) {
+    return nr == 2 ? 0x54u : (nr == 3 ? 0x520u : 0x3120u);   // 2: L, R;  3: UL, LL, R;  4: UL, LL, UR, LR
 }
 
 // keys placed in room r given the agent's room ar: kA, kB door indices (-1 none);
@@ -885,8 +884,6 @@ __device__ __forceinline__ void key_spec(int nr, int r, int ar, int &kA, int &kB
         if (ar == 3) { kA = VL; kB = HR; } else if (ar == 1) kA = HR; else if (ar == 2) kA = VL;
     }
 }
-
-__device__ const int MULTI_TYPES[3] = {T_KEY, T_BALL, T_BOX};
 
 // ---- the MT-only prefix of a multi-room attempt (round 6) -----------------------------------------------------
 // Everything gen_multi / gen_rooms draw before their first PCG64 draw comes from the shared MT19937 stream only:
@@ -1137,17 +1134,34 @@ __device__ __forceinline__ void gen_rooms(Gen<NW> &G, const Prefix &P) {
         else { c3 -= ndec; n = c3; }
         npack |= (uint32_t)(n > 0 ? n : 0) << (8 * r);
     }
-    // The keys and objects of all rooms as ONE task sequence: every outer iteration places
-    // one key or object for every lane, whatever room/task the lane is at (lanes do not wait
-    // for each other at room boundaries).  Each lane still draws exactly the reference's
-    // sequence:  for room r: [key A] [key B] then n_r x { choice(obj_choice); position loop }.
-    // The rejection loop `while True: p = (randint(x0,x1), randint(y0,y1)); if ok(p): break`
-    // is the tight inner loop: the cells a placement must avoid are one precomputed bit set,
-    // so a rejected draw costs two SWAR randbelow and one bit test -- the lanes that need many
-    // draws (the wave waits for them) no longer re-run the task set-up per draw.
-    uint64_t reps = 0;                       // bit y*S of every row y (S <= 8): room masks by multiply
-    if (NW == 1)
+    // The keys and objects of all rooms as ONE task sequence and ONE loop over the placement draws' ten-word
+    // passes (round 18): an iteration is one pass (cell_pass) for every lane that still has a task, whatever
+    // room / task / pass of it the lane is at.  A lane whose cell is accepted commits the placement and advances
+    // `todo` in the same iteration, and sets up its next task at the top of the next one (`fresh`), whose pass
+    // already serves that task: lanes wait for each other neither at room nor at task boundaries.  Each lane
+    // still draws exactly the reference's sequence:
+    //   for room r: [key A] [key B] then n_r x { choice(obj_choice); position loop }
+    // with `while True: p = (randint(x0,x1), randint(y0,y1)); if ok(p): break` as the candidate loop of the pass:
+    // the cells a placement must avoid are one precomputed bit set (S <= 11).
+    // The loop has one way out, `todo == 0`: a lane that is abandoned (the cap inside a pass, no acceptable cell)
+    // or has run out of object choices clears its `todo`; why is in G.abort (the cursor at the cap) or G.err.
+    // What a task's set-up needs of its room depends on (nr, r, S) only: two bits of x / y class per room, packed
+    // per attempt, select the room's corner, its randbelow constants and its cell mask from constants of S
+    // (formed once per attempt; compile-time constants where S is a template constant).
+    const int wa = mid - 1, wb = S - 2 - mid;        // widths: classes A (left / upper), B (right / lower), F (full height)
+    const RbConst KA = rb_const((uint32_t)wa), KB = rb_const((uint32_t)wb), KF = rb_const((uint32_t)(S - 2));
+    uint64_t colA = 0, colB = 0, rowA = 0, rowB = 0, rowF = 0;   // S <= 8: a room's cells = its columns & its rows
+    if (NW == 1) {
+        uint64_t reps = 0;                   // bit y*S of every row y
         for (int i = 0; i < S; i++) reps |= 1ull << (i * S);
+        colA = reps * (uint64_t)(((1u << wa) - 1u) << 1);
+        colB = reps * (uint64_t)(((1u << wb) - 1u) << (mid + 1));
+        rowA = ((1ull << (mid * S)) - 1ull) & ~((1ull << S) - 1ull);
+        rowB = ((1ull << ((S - 1) * S)) - 1ull) & ~((1ull << ((mid + 1) * S)) - 1ull);
+        rowF = ((1ull << ((S - 1) * S)) - 1ull) & ~((1ull << S) - 1ull);
+    }
+    const uint32_t geo = room_classes(nr);
+    const int bgoal = gy * S + gx, bagent = G.ay * S + G.ax;
     // The task sequence as one 64-bit set, consumed lowest bit first: room r owns bits 16r..16r+15,
     // bit 0 of a room = key A, bit 1 = key B, bits 2.. = its objects (<= 9, num_objects <= 18).
     // Advancing is `todo &= todo - 1` (a per-lane walk over rooms / phases was a divergent loop).
@@ -1158,92 +1172,109 @@ __device__ __forceinline__ void gen_rooms(Gen<NW> &G, const Prefix &P) {
                 << (16 * rr);
     if (MGX_GEN_SKIP & 1) return;
     int kx = -1, ky = -1;                    // this room's key A (key B avoids it)
+    // the lane's current task: room corner and widths, randbelow constants, the cells it rejects (S <= 11: `bad`;
+    // else the three excluded cells e0..e2, -1 = none, and whether occupied cells count), the decoder's state
+    bool fresh = true, objtask = false;
+    int x0 = 0, y0 = 0, wx = 0, wy = 0, e0 = -1, e1 = -1, e2 = -1;
+    RbConst KX = KA, KY = KA, KC = KA;
+    Bits<NW> bad;
+    bad.clear();
+    bool need_c = false, have_x = false;
+    uint32_t xv = 0;
+    int rej = 0, choice = 0;
 #pragma unroll 1
     while (todo) {
-        GCOUNT(G, 20);
         GSTAMP(G, 19);                                           // (commit + task advance of the previous)
-        GSTAMP(G, 16);                                           // MT window top-up
-        const int slot = (int)__builtin_ctzll(todo);
-        const int r = slot >> 4, phase = min(slot & 15, 2);     // 0 key A, 1 key B, 2 object
-        int x0, x1, y0, y1;
-        room_rect(nr, r, mid, S, x0, x1, y0, y1);
-        const bool is_key = phase < 2;
-        int cname, ot = T_KEY, ox = -1, oy = -1;
-        bool chk = false, kib = false;
-        if (is_key) {
-            chk = (kspec >> (16 + r)) & 1;
-            const uint32_t di = dinfo >> (8 * ((kspec >> (4 * r + 2 * phase)) & 3));
-            cname = di & 7;
-            kib = (di >> 4) & 1;
-            if (phase == 1 && ((keymask >> (2 * r)) & 1)) { ox = kx; oy = ky; }   // key A came just before
-        } else {
-            if (oc == 0) { G.err |= 8u; break; }
-            // the object's random.choice(obj_choice) is the first draw of its placement's rejection loop's
-            // first pass (draw_cell has_c); the type and colour are taken once the cell is drawn
+        if (fresh) {
+            GCOUNT(G, 20);
+            const int slot = (int)__builtin_ctzll(todo);
+            const int r = slot >> 4, ph = slot & 15;             // 0 key A, 1 key B, 2.. object
+            const bool is_key = ph < 2;
+            const uint32_t gq = geo >> (4 * r);
+            const bool xb = gq & 1u, yb = gq & 2u, yf = gq & 4u;
+            x0 = xb ? mid + 1 : 1;
+            wx = xb ? wb : wa;
+            KX.c1 = xb ? KB.c1 : KA.c1; KX.sh = xb ? KB.sh : KA.sh;
+            y0 = yb ? mid + 1 : 1;
+            wy = yf ? S - 2 : (yb ? wb : wa);
+            KY.c1 = yf ? KF.c1 : (yb ? KB.c1 : KA.c1); KY.sh = yf ? KF.sh : (yb ? KB.sh : KA.sh);
+            // the object's random.choice(obj_choice) is the first draw of its placement's first pass (need_c); the
+            // type and colour are taken once the cell is drawn.  No choice left: excluded by validation -> G.err
+            const bool none = !is_key && oc == 0u;
+            G.err |= none ? 8u : 0u;
+            KC = rb_const(is_key ? 1u : (uint32_t)__popc(oc));
+            // cells this placement rejects: key -> goal, [agent], [this room's key A], next to a door;
+            // object -> occupied, agent, next to a door
+            const bool chk = (kspec >> (16 + r)) & 1u;
+            const bool other = ph == 1 && ((keymask >> (2 * r)) & 1u);    // key A came just before
+            objtask = !is_key;
+            e0 = is_key ? bgoal : -1;
+            e1 = (!is_key || chk) ? bagent : -1;
+            e2 = other ? ky * S + kx : -1;
+            bool sat = true;
+            if constexpr (NW <= 2) {
+                bad = G.dn;
+                bad.w0 |= is_key ? 0ull : G.occ.w0;
+                if (NW > 1) bad.w1 |= is_key ? 0ull : G.occ.w1;
+                bad.set(e0);                                     // (-1 sets nothing)
+                bad.set(e1);
+                bad.set(e2);
+                if constexpr (NW == 1) sat = ((xb ? colB : colA) & (yf ? rowF : (yb ? rowB : rowA)) & ~bad.w0) != 0;
+                else sat = rect_has_free(bad, x0, wx, y0, wy, S);
+            }
+            // no acceptable cell in the room: the reference's loop never ends -> live-lock policy at once (the
+            // choice draw before it changes nothing: the attempt's cursor jumps to its cap either way)
+            if (!none && !sat) live_lock(G);
+            todo = (none || !sat) ? 0ull : todo;
+            need_c = !is_key && !(MGX_GEN_SKIP & 32);
+            have_x = false;
+            xv = 0;
+            rej = 0;
+            choice = 0;
+            fresh = false;
         }
-        const bool has_c = !is_key && !(MGX_GEN_SKIP & 32);
-        const RbConst kc_ = rb_const(is_key ? 1u : (uint32_t)__popc(oc));
-        int choice = 0;
-        // cells this placement rejects: key -> goal, [agent], [the other key], next to a door;
-        // object -> occupied, agent, next to a door
-        const int ex0 = is_key ? gx : G.ax, ey0 = is_key ? gy : G.ay;
-        const int ex1 = (is_key && !chk) ? -1 : G.ax, ey1 = (is_key && !chk) ? -1 : G.ay;
-        const RbConst kx_ = rb_const((uint32_t)(x1 - x0 + 1)), ky_ = rb_const((uint32_t)(y1 - y0 + 1));
-        int x, y;
-        GSTAMP(G, 17);                                           // task set-up, choice, satisfiability
-        if constexpr (NW <= 2) {
-            Bits<NW> bad = G.dn;
-            if (!is_key) { bad.w0 |= G.occ.w0; if (NW > 1) bad.w1 |= G.occ.w1; }
-            bad.set(ey0 * S + ex0);
-            if (ex1 >= 0) bad.set(ey1 * S + ex1);
-            if (ox >= 0) bad.set(oy * S + ox);
-            // no acceptable cell in the room: the reference's loop never ends -> live-lock policy
-            // at once (same end state as after the word cap)
-            bool sat;
-            if constexpr (NW == 1) {
-                const uint64_t rows = reps & (((1ull << ((y1 + 1) * S)) - 1ull) & ~((1ull << (y0 * S)) - 1ull));
-                sat = ((rows * (uint64_t)(((1u << (x1 - x0 + 1)) - 1u) << x0)) & ~bad.w0) != 0;
+        GSTAMP(G, 17);                                           // task set-up, satisfiability
+        if (todo) {
+            int x, y;
+            bool ok;
+            if constexpr (NW <= 2) {
+                ok = cell_pass(G, KX, KY, x0, y0, x, y, [&](int cx, int cy) { return bad.test(cy * S + cx); },
+                               [] { return true; }, KC, choice, need_c, have_x, xv, rej);
             } else {
-                sat = rect_has_free(G, x0, x1, y0, y1, !is_key, ex0, ey0, ex1, ey1, ox, oy);
+                // S > 11: the cells are tested in the LDS grid; after SAT_PROBE rejections an exhaustive
+                // scan of the room decides whether the loop can end (else the live-lock policy)
+                const auto badc = [&](int cx, int cy) {
+                    const int b = cy * S + cx;
+                    return b == e0 || b == e1 || b == e2 || (objtask && occupied(G, b)) || next2door(G, cx, cy);
+                };
+                ok = cell_pass(G, KX, KY, x0, y0, x, y, badc, [&] {
+                    for (int xx = x0; xx < x0 + wx; xx++)
+                        for (int yy = y0; yy < y0 + wy; yy++)
+                            if (!badc(xx, yy)) return true;
+                    return false;
+                }, KC, choice, need_c, have_x, xv, rej);
             }
-            if (!sat) {
-                // no acceptable cell: the reference's loop never ends -> live-lock policy at once (the choice
-                // draw before it changes nothing: the attempt's cursor jumps to its cap either way)
-                live_lock(G);
-                return;
+            GSTAMP(G, 18);                                       // the pass
+            if (ok) {                                            // commit the placement; the next task is set up above
+                const int slot = (int)__builtin_ctzll(todo);
+                const int r = slot >> 4, ph = slot & 15;
+                const bool is_key = ph < 2;
+                // key: colour and key-in-box of its door; object: the type and colour of its choice
+                const uint32_t di = dinfo >> (8 * ((kspec >> (4 * r + 2 * (ph & 1))) & 3));
+                const int b = (MGX_GEN_SKIP & 32) ? __ffs(oc) - 1 : nth_set_bit(oc, choice);
+                oc &= is_key ? ~0u : ~(1u << b);
+                const int cname = is_key ? (int)(di & 7u) : b % 6;
+                const bool kib = is_key && ((di >> 4) & 1u);
+                const int t = is_key ? (kib ? T_BOX : T_KEY) : (b < 6 ? T_KEY : (b < 12 ? T_BALL : T_BOX));
+                put(G, x, y, mk_code(t, cn2idx(cname), kib ? 1 : 0));
+                add_obj(G, t, cname, x, y, is_key ? OBJ_KEYFLAG : 0u);
+                kx = ph == 0 ? x : kx;
+                ky = ph == 0 ? y : ky;
+                todo &= todo - 1;
+                fresh = true;
             }
-            draw_cell(G, kx_, ky_, x0, y0, x, y, [&](int cx, int cy) { return bad.test(cy * S + cx); },
-                      [] { return true; }, has_c, kc_, choice);
-            if (G.abort) return;
-        } else {
-            // S > 11: the cells are tested in the LDS grid; after SAT_PROBE rejections an exhaustive
-            // scan of the room decides whether the loop can end (else the live-lock policy)
-            const auto bad = [&](int cx, int cy) {
-                return (cx == ex0 && cy == ey0) || (cx == ex1 && cy == ey1) || (cx == ox && cy == oy) ||
-                       (!is_key && occupied(G, cy * S + cx)) || next2door(G, cx, cy);
-            };
-            draw_cell(G, kx_, ky_, x0, y0, x, y, bad, [&] {
-                for (int xx = x0; xx <= x1; xx++)
-                    for (int yy = y0; yy <= y1; yy++)
-                        if (!bad(xx, yy)) return true;
-                return false;
-            }, has_c, kc_, choice);
-            if (G.abort) return;
+            todo = G.abort ? 0ull : todo;
         }
-        if (!is_key) {                                           // commit the object's type and colour
-            const int b = (MGX_GEN_SKIP & 32) ? __ffs(oc) - 1 : nth_set_bit(oc, choice);
-            oc &= ~(1u << b);
-            ot = MULTI_TYPES[b / 6];
-            cname = b % 6;
-        }
-        GSTAMP(G, 18);                                           // inner rejection loop
-        // commit the placement, then the next task
-        const int cidx = cn2idx(cname);
-        const int t = is_key ? (kib ? T_BOX : T_KEY) : ot;
-        put(G, x, y, mk_code(t, cidx, (is_key && kib) ? 1 : 0));
-        add_obj(G, t, cname, x, y, is_key ? OBJ_KEYFLAG : 0u);
-        if (phase == 0) { kx = x; ky = y; }
-        todo &= todo - 1;
     }
     GSTAMP(G, 14);                                               // keys + objects, room by room
 }

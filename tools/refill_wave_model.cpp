@@ -10,9 +10,13 @@
 //       -Iminigrid-rl_amd/csrc -o refill_wave_model tools/refill_wave_model.cpp
 //   ./refill_wave_model --mission 5 --size 8 --envs 4096 --episodes 11 [--wave 64] [--llw 4096] [--cursors FILE]
 //
-// Sites (mgx_device.h): 20 key/object task, 27 draw_cell pass, 25 draw_cell candidate iteration, 26 word-by-word
+// Sites (mgx_device.h): 20 key/object task, 27 placement pass (cell_pass), 25 its candidate iteration, 26 word-by-word
 // tail entered (builds that still have one), 21 randbelow pass, 24 randbelow call, 22 goal/agent PCG64 iteration,
-// 23 MT window reload.  The host draws every MT-only prefix (the kernel looks most of them up in its prefix
+// 23 MT window reload.
+// Round 18 runs all tasks of an attempt through ONE loop over passes: a lane's p-th pass of the attempt, whatever
+// task it serves, runs beside every other lane's p-th pass.  "flat_passes" / "flat_cand_iters" are the union counts
+// of that loop (the most passes any lane takes; per pass the most candidates), "tasks" / "draw_passes" /
+// "cand_iters" those of the task loop around a pass loop that the builds before it have.  The host draws every MT-only prefix (the kernel looks most of them up in its prefix
 // records): those passes are reported apart ("prefix_passes") and are no part of the round's model.
 #include <cstdio>
 #include <cstdlib>
@@ -59,8 +63,8 @@ using namespace hostlane;
 
 namespace {
 const char *NAMES[] = {"tasks", "draw_passes", "cand_iters", "tail_entries", "tail_rb_passes", "goal_agent_iters",
-                       "post_rb_passes", "prefix_passes", "window_reloads"};
-constexpr int NC = 9;
+                       "post_rb_passes", "prefix_passes", "window_reloads", "flat_passes", "flat_cand_iters"};
+constexpr int NC = 11;
 
 template <int NW>
 int run(const Config &c, int n, int W, int64_t seed, int episodes, const char *cursors) {
@@ -99,6 +103,10 @@ int run(const Config &c, int n, int W, int64_t seed, int episodes, const char *c
                     for (int v : a.tailrb[(size_t)t]) lane[4] += v;
                 }
                 lane[5] += a.ga; lane[6] += a.post; lane[7] += a.pre; lane[8] += a.reload;
+                for (int t = 0; t < a.tasks; t++) {              // (a lane's own counts do not depend on the loop's shape)
+                    lane[9] += a.passes[(size_t)t];
+                    for (int v : a.cand[(size_t)t]) lane[10] += v;
+                }
                 if ((size_t)a.tasks > mt) mt = (size_t)a.tasks;
             }
             // wave unions: the maximum over the lanes per enclosing iteration
@@ -110,6 +118,23 @@ int run(const Config &c, int n, int W, int64_t seed, int episodes, const char *c
                 if (a.reload > u8) u8 = a.reload;
             }
             wave[0] += (double)mt; wave[5] += u5; wave[6] += u6; wave[7] += u7; wave[8] += u8;
+            {   // one loop over passes: the lane's passes of all its tasks in a row
+                std::vector<std::vector<int>> flat;
+                size_t fp = 0;
+                for (const auto &a : A) {
+                    flat.emplace_back();
+                    for (int t = 0; t < a.tasks; t++)
+                        for (int v : a.cand[(size_t)t]) flat.back().push_back(v);
+                    if (flat.back().size() > fp) fp = flat.back().size();
+                }
+                wave[9] += (double)fp;
+                for (size_t p = 0; p < fp; p++) {
+                    int uc = 0;
+                    for (const auto &f : flat)
+                        if (f.size() > p && f[p] > uc) uc = f[p];
+                    wave[10] += uc;
+                }
+            }
             for (size_t t = 0; t < mt; t++) {
                 size_t mp = 0;
                 for (const auto &a : A)

@@ -7,7 +7,7 @@ and prices the union counts with the static VALU / SALU counts of the same block
 (hipcc -O3 --offload-arch=gfx950 -S, the kernel's loops by their back edges; each block's OWN instructions, its
 inner loops taken out).  Modelled instructions per attempt round = sum over blocks of own count x union trips.
 
-  python tools/refill_wave_model.py [--build r07|r06] [--mission 5] [--envs 4096] [--episodes 11] [--wave 64]
+  python tools/refill_wave_model.py [--build r18|r07|r06] [--mission 5] [--envs 4096] [--episodes 11] [--wave 64]
                                     [--llw 4096] [--binary PATH] [--out FILE]
 
 The static counts are a table in this file, per build: update it (the comment beside each entry names the loop)
@@ -38,6 +38,13 @@ STATIC = {
         "task loop own":            (415 - 123, 186 - 63, "tasks"),
         "draw_cell pass own":       (123 - 26, 63 - 23, "draw_passes"),
         "draw_cell candidate loop": (26, 23, "cand_iters"),
+        "goal/agent loop":          (65, 26, "goal_agent_iters"),
+    },
+    # round 18: one loop over the passes of all tasks (task set-up and commit inside it, single exit), per-room
+    # constants selected from constants of S.  Priced with the flattened union counts
+    "r18": {
+        "task + pass loop own":     (317 - 27, 94 - 16, "flat_passes"),       # while (todo) body less the candidate loop
+        "candidate loop":           (27, 16, "flat_cand_iters"),
         "goal/agent loop":          (65, 26, "goal_agent_iters"),
     },
 }
@@ -73,7 +80,7 @@ def price(counts, build):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--build", default="r07", choices=sorted(STATIC))
+    ap.add_argument("--build", default="r18", choices=sorted(STATIC))
     ap.add_argument("--mission", type=int, default=5, help="-1: drawn (config 4)")
     ap.add_argument("--size", type=int, default=8)
     ap.add_argument("--envs", type=int, default=4096)
