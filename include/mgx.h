@@ -328,6 +328,64 @@ mgx_status mgx_policy_bootstrap(const mgx_handle *h, const uint8_t *rows_dev, co
                                 const uint8_t *terminal_rows_dev, const mgx_policy *pol, const mgx_bootstrap *b,
                                 void *stream);
 
+/* ---- Mission-routed mixture of experts (added within ABI 9) ------------------------------------------
+ * mgx_policy_act over up to MGX_MOE_MAX_EXPERTS frozen policies of one n_stack: sample b (position b of
+ * index_dev) is computed with the weight blob and the mission-feature table of expert
+ *    e(b) = route_dev[mission_ids_dev[index_dev[b]]]
+ * -- the mission id of the sample's newest frame, terminal case included -- and is, bit for bit, what
+ * mgx_policy_act returns for it with that expert's mgx_policy, the same seed and the same counter value.  The
+ * reference's mixture (src/policies.py MoeExtractor: the arg-max of a gate over the newest frame's mission
+ * tokens picks one of the per-task policies) with the gate tabulated per mission id.  Two launches:
+ *
+ * (1) the route: ONE workgroup partitions the positions p in [0, n_samples) by expert, stably.  Expert e's
+ *     segment of the lists starts at start_e = 64 * sum over e' < e of ceil(count_e' / 64) and holds count_e
+ *     entries with ascending p.  A sample whose route byte is >= n_experts is unroutable: it is counted, left out
+ *     of every list, and none of its outputs is written.  In mode 2 this launch also snapshots counter_dev[0]
+ *     into the record and advances it by one (launch 2's grid holds idle workgroups, so mgx_policy_act's
+ *     arrival tally is not used; every draw uses the snapshot, the value before the advance).
+ * (2) the policy pass: a grid of (n_samples + 63 * n_experts) / 64 workgroups, the bound on the live tiles
+ *     sum_e ceil(count_e / 64); a workgroup past the live tile count exits after one load; a live one finds its
+ *     expert among the <= 8 segment records and runs mgx_policy_act's forward pass and heads on its tile of 64
+ *     list entries with that expert's weights.  Outputs go to position p, and the sampling hash is keyed by p.
+ *
+ * scratch_dev: caller-owned, 8-byte aligned, mgx_policy_moe_scratch_words(n_samples, n_experts) i32 words, not
+ * zeroed by anyone: every word launch 2 reads is written by launch 1, and all of it stays readable afterwards.
+ * With cap = n_samples + 63 * n_experts (the most entries a list can hold):
+ *    words [0, 32)               the record: [2e] = start_e, [2e + 1] = count_e for e < 8 (experts >= n_experts:
+ *                                start = the end of the last segment, count 0), [16] = live tiles, [17] = unroutable
+ *                                samples, [18..19] = the u64 counter snapshot (0 unless mode 2), [20..31] = 0
+ *    words [32, 32 + 2 cap)      i64 list[cap]: list[start_e + j] = index_dev[p] of the j-th position p of expert e
+ *    words [32 + 2 cap, 32 + 3 cap)  i32 pos[cap]: that p
+ * List entries outside [start_e, start_e + count_e) (the padding up to a multiple of 64) are never written. */
+#define MGX_MOE_MAX_EXPERTS 8
+#define MGX_MOE_RECORD_WORDS 32
+
+/* host only: 32 + 3 * (n_samples + 63 * n_experts); -1 unless n_samples > 0, 1 <= n_experts <= 8 and
+ * n_samples + 63 * n_experts < 2^31 */
+int64_t mgx_policy_moe_scratch_words(int64_t n_samples, int n_experts);
+
+typedef struct mgx_policy_moe {
+    int32_t n_experts;              /* 1 .. MGX_MOE_MAX_EXPERTS */
+    int32_t mode;                   /* as mgx_policy */
+    const float *blob_dev[MGX_MOE_MAX_EXPERTS];          /* the first n_experts: as mgx_policy.blob_dev */
+    const float *mission_feat_dev[MGX_MOE_MAX_EXPERTS];  /* the first n_experts: as mgx_policy.mission_feat_dev */
+    const uint8_t *route_dev;       /* u8 [256]: mission id -> expert */
+    uint64_t seed;                  /* mode 2 */
+    uint64_t *counter_dev;          /* mode 2: as mgx_policy; the PAIR of launches advances counter_dev[0] by one */
+    int32_t *scratch_dev;           /* i32 [scratch_words], 8-byte aligned (layout above) */
+    int64_t scratch_words;          /* >= mgx_policy_moe_scratch_words(n_samples, n_experts) */
+} mgx_policy_moe;
+
+/* rows_dev .. terminal_rows_dev and out: exactly mgx_policy_act's.  Only enqueues on `stream` (no allocation, no
+ * host sync; capturable).  MGX_ERR_INVALID before any HIP call for: null pol / out / route_dev / scratch_dev or
+ * one of the first n_experts blob or table pointers, n_experts outside 1..8, a misaligned scratch_dev,
+ * scratch_words below mgx_policy_moe_scratch_words (or n_samples beyond its range), and every case
+ * mgx_policy_act rejects. */
+mgx_status mgx_policy_act_moe(const mgx_handle *h, const uint8_t *rows_dev, const uint8_t *mission_ids_dev,
+                              const uint8_t *starts_dev, int64_t n_envs, int64_t ring_rows,
+                              const int64_t *index_dev, int64_t n_samples, const uint8_t *terminal_rows_dev,
+                              const mgx_policy_moe *pol, const mgx_act_out *out, void *stream);
+
 /* ---- Fused policy gradient over compact rows (ABI 9) ---------------------------------------------
  * The backward pass of the network above for the same kind of samples, for the PPO update: given the
  * cotangents of action_net's and value_net's outputs it recomputes the forward pass from the compact rows

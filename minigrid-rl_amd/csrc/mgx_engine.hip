@@ -3250,6 +3250,9 @@ mgx_status mgx_create(const mgx_config *cfg, int device, mgx_handle **out) {
             pol_lds = hipFuncSetAttribute((const void *)mgx_policy_boot_kernel<KK>,
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)pol_lds_bytes(KK));
         if (pol_lds == hipSuccess)
+            pol_lds = hipFuncSetAttribute((const void *)mgx_policy_moe_kernel<KK>,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)pol_lds_bytes(KK));
+        if (pol_lds == hipSuccess)
             pol_grad_lds = hipFuncSetAttribute((const void *)mgx_policy_grad_kernel<KK>,
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)pg_lds_bytes());
     });
@@ -3894,6 +3897,64 @@ mgx_status mgx_policy_bootstrap(const mgx_handle *h, const uint8_t *rows_dev, co
     for_n_stack(K, [&](auto kk) {
         constexpr int KK = decltype(kk)::value;
         hipLaunchKernelGGL(mgx_policy_boot_kernel<KK>, dim3(groups), dim3(POL_THREADS), pol_lds_bytes(KK),
+                           (hipStream_t)stream, a);
+    });
+    HIP_TRY(hipGetLastError());
+    return MGX_OK;
+}
+
+int64_t mgx_policy_moe_scratch_words(int64_t n_samples, int n_experts) {
+    if (n_samples <= 0 || n_experts < 1 || n_experts > MOE_MAX) return -1;
+    if (n_samples > (int64_t)INT32_MAX - (POL_TILE - 1) * n_experts) return -1;    // positions and slots are i32
+    return MOE_REC + 3 * (n_samples + (POL_TILE - 1) * n_experts);
+}
+
+mgx_status mgx_policy_act_moe(const mgx_handle *h, const uint8_t *rows_dev, const uint8_t *mission_ids_dev,
+                              const uint8_t *starts_dev, int64_t n_envs, int64_t ring_rows,
+                              const int64_t *index_dev, int64_t n_samples, const uint8_t *terminal_rows_dev,
+                              const mgx_policy_moe *pol, const mgx_act_out *out, void *stream) {
+    if (!pol || !out) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: null policy / outputs");
+    if (pol->n_experts < 1 || pol->n_experts > MOE_MAX)
+        return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: n_experts must be 1..8");
+    for (int e = 0; e < pol->n_experts; e++)
+        if (!pol->blob_dev[e] || !pol->mission_feat_dev[e])
+            return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: null blob / mission features of an expert");
+    if (!pol->route_dev || !pol->scratch_dev) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: null route / scratch");
+    if ((uintptr_t)pol->scratch_dev & 7) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: scratch_dev must be 8-byte aligned");
+    if (n_samples <= 0) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: n_samples must be > 0");
+    if (pol->mode < 0 || pol->mode > 2) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: mode must be 0, 1 or 2");
+    if (pol->mode == 2 && !pol->counter_dev) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: mode 2 needs counter_dev");
+    if (pol->mode != 0 && (!out->actions_dev || !out->log_probs_dev))
+        return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: modes 1 and 2 need actions_dev and log_probs_dev");
+    const int64_t words = mgx_policy_moe_scratch_words(n_samples, pol->n_experts);
+    if (words < 0) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: n_samples out of range");
+    if (pol->scratch_words < words)
+        return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: scratch_words below mgx_policy_moe_scratch_words");
+    PolMoeArgs a;
+    const int bad = sample_addr(h, rows_dev, mission_ids_dev, starts_dev, n_envs, ring_rows, index_dev, n_samples, &a.s);
+    if (bad == 1) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: bad sample addressing");
+    if (bad == 2) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: the ring must hold n_stack rows");
+    const int K = h->kp.n_stack;
+    if (K < 1 || K > MAX_NSTACK) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: n_stack out of range");
+    const int64_t cap = n_samples + (POL_TILE - 1) * pol->n_experts;   // the most entries a list can hold
+    a.newest = terminal_rows_dev;
+    for (int e = 0; e < MOE_MAX; e++) {
+        a.blob[e] = e < pol->n_experts ? pol->blob_dev[e] : nullptr;
+        a.mfeat[e] = e < pol->n_experts ? pol->mission_feat_dev[e] : nullptr;
+    }
+    a.route = pol->route_dev; a.n_experts = pol->n_experts; a.mode = pol->mode; a.seed = pol->seed;
+    a.ctr = (unsigned long long *)pol->counter_dev;
+    a.rec = pol->scratch_dev;
+    a.list = reinterpret_cast<int64_t *>(pol->scratch_dev + MOE_REC);
+    a.pos = pol->scratch_dev + MOE_REC + 2 * cap;
+    a.actions = (long long *)out->actions_dev; a.values = out->values_dev; a.log_probs = out->log_probs_dev;
+    a.logits = out->logits_dev;
+    hipLaunchKernelGGL(mgx_moe_route_kernel, dim3(1), dim3(MOE_THREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    const unsigned groups = (unsigned)(cap / POL_TILE);               // >= the live tiles (mgx_policy_moe_kernel)
+    for_n_stack(K, [&](auto kk) {
+        constexpr int KK = decltype(kk)::value;
+        hipLaunchKernelGGL(mgx_policy_moe_kernel<KK>, dim3(groups), dim3(POL_THREADS), pol_lds_bytes(KK),
                            (hipStream_t)stream, a);
     });
     HIP_TRY(hipGetLastError());

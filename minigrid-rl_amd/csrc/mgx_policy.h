@@ -334,10 +334,64 @@ __device__ __forceinline__ void pol_l1(const float *__restrict__ W, int wv, int 
     }
 }
 
+// ---- G: action_net and value_net on H2 = P, then the action choice and the outputs of sample b (= the lane's, if
+// `live`): wave 0 of mgx_policy_kernel and of mgx_policy_moe_kernel, one sample per lane.  b is the sample's position
+// in the caller's index: where its outputs go and what keys its draw.  read_ctr() loads the launch counter (mode 2
+// only, by the whole wave, after the heads' dots); the value is returned (0 in the other modes).
+template <int K, class ReadCtr>
+__device__ __forceinline__ unsigned long long pol_heads(const float *__restrict__ W, const float *P, int lane, bool live,
+                                                        int64_t b, int mode, uint64_t seed, ReadCtr read_ctr,
+                                                        long long *actions, float *values, float *log_probs,
+                                                        float *logits) {
+    constexpr PolBlob L = pol_blob(K);
+    constexpr int LS = POL_LS;
+    float lg[POL_NA], val[1];
+#pragma unroll
+    for (int o = 0; o < POL_NA; o++) lg[o] = W[L.a_b + o];
+    val[0] = W[L.vn_b];
+    pol_dot<POL_NA>(lg, W + L.a_w, 64, 64, pol_lds4(P + lane));
+    pol_dot<1>(val, W + L.vn_w, 64, 64, pol_lds4(P + 64 * LS + lane));
+    unsigned long long c = 0;
+    if (mode == 2) c = read_ctr();
+    if (live) {
+        if (values) values[b] = val[0];
+        if (logits) {
+#pragma unroll
+            for (int o = 0; o < POL_NA; o++) logits[b * POL_NA + o] = lg[o];
+        }
+        if (mode != 0) {
+            float mx = lg[0];
+            int am = 0;
+#pragma unroll
+            for (int o = 1; o < POL_NA; o++)
+                if (lg[o] > mx) { mx = lg[o]; am = o; }              // first index of the maximum
+            float cum[POL_NA], tot = 0.0f;
+#pragma unroll
+            for (int o = 0; o < POL_NA; o++) { tot = tot + expf(lg[o] - mx); cum[o] = tot; }
+            int act = am;
+            if (mode == 2) {
+                const uint64_t key = splitmix64(seed + (uint64_t)c * 0x9E3779B97F4A7C15ull);
+                const uint64_t h = splitmix64(key ^ ((uint64_t)b * 0xD1B54A32D192ED03ull));
+                const float u = (float)(uint32_t)(h >> 40) * (1.0f / 16777216.0f);
+                const float thr = u * tot;
+                act = POL_NA - 1;
+#pragma unroll
+                for (int o = POL_NA - 2; o >= 0; o--)
+                    if (cum[o] > thr) act = o;                        // ends at the smallest such index
+            }
+            float la = lg[0];
+#pragma unroll
+            for (int o = 1; o < POL_NA; o++) la = act == o ? lg[o] : la;
+            actions[b] = act;
+            log_probs[b] = (la - mx) - logf(tot);
+        }
+    }
+    return c;
+}
+
 template <int K>
 __global__ __launch_bounds__(POL_THREADS, 4) void mgx_policy_kernel(PolArgs a) {
     extern __shared__ __align__(16) uint8_t smem[];
-    constexpr PolBlob L = pol_blob(K);
     constexpr int LS = POL_LS;
     float *X = reinterpret_cast<float *>(smem);                       // [pol_x_rows][65]
     float *P = X + pol_x_rows(K) * LS;                                // [144][65]
@@ -370,48 +424,10 @@ __global__ __launch_bounds__(POL_THREADS, 4) void mgx_policy_kernel(PolArgs a) {
     __syncthreads();
     // ---- G: heads, action choice and outputs: wave 0, one sample per lane
     if (wv != 0) return;
-    float lg[POL_NA], val[1];
-#pragma unroll
-    for (int o = 0; o < POL_NA; o++) lg[o] = W[L.a_b + o];
-    val[0] = W[L.vn_b];
-    pol_dot<POL_NA>(lg, W + L.a_w, 64, 64, pol_lds4(P + lane));
-    pol_dot<1>(val, W + L.vn_w, 64, 64, pol_lds4(P + 64 * LS + lane));
-    unsigned long long c = 0;
-    if (a.mode == 2) c = *reinterpret_cast<volatile unsigned long long *>(a.ctr);
-    if (lane < nb) {
-        const int64_t b = b0 + lane;
-        if (a.values) a.values[b] = val[0];
-        if (a.logits) {
-#pragma unroll
-            for (int o = 0; o < POL_NA; o++) a.logits[b * POL_NA + o] = lg[o];
-        }
-        if (a.mode != 0) {
-            float mx = lg[0];
-            int am = 0;
-#pragma unroll
-            for (int o = 1; o < POL_NA; o++)
-                if (lg[o] > mx) { mx = lg[o]; am = o; }              // first index of the maximum
-            float cum[POL_NA], tot = 0.0f;
-#pragma unroll
-            for (int o = 0; o < POL_NA; o++) { tot = tot + expf(lg[o] - mx); cum[o] = tot; }
-            int act = am;
-            if (a.mode == 2) {
-                const uint64_t key = splitmix64(a.seed + (uint64_t)c * 0x9E3779B97F4A7C15ull);
-                const uint64_t h = splitmix64(key ^ ((uint64_t)b * 0xD1B54A32D192ED03ull));
-                const float u = (float)(uint32_t)(h >> 40) * (1.0f / 16777216.0f);
-                const float thr = u * tot;
-                act = POL_NA - 1;
-#pragma unroll
-                for (int o = POL_NA - 2; o >= 0; o--)
-                    if (cum[o] > thr) act = o;                        // ends at the smallest such index
-            }
-            float la = lg[0];
-#pragma unroll
-            for (int o = 1; o < POL_NA; o++) la = act == o ? lg[o] : la;
-            a.actions[b] = act;
-            a.log_probs[b] = (la - mx) - logf(tot);
-        }
-    }
+    const unsigned long long c = pol_heads<K>(
+        W, P, lane, lane < nb, b0 + lane, a.mode, a.seed,
+        [&] { return *reinterpret_cast<volatile unsigned long long *>(a.ctr); }, a.actions, a.values, a.log_probs,
+        a.logits);
     // the launch counter, as mgx_random_actions_kernel: every workgroup has read it (above, the whole wave) before its
     // own tally add; the last one to arrive advances it
     if (a.mode == 2 && tid == 0) {
@@ -520,6 +536,175 @@ __global__ __launch_bounds__(POL_THREADS, 4) void mgx_policy_boot_kernel(PolBoot
         a.rewards[e] = __fadd_rn(a.rewards[e], gv);
         if (a.values) a.values[b0 + lane] = val[0];
     }
+}
+
+// ---- mgx_policy_act_moe: mgx_policy_act with the weights of expert route[mission id of the newest frame] per sample
+// (DESIGN.md "Mission-routed mixture of experts").  Two launches, the shape of the bootstrap's pair above.
+constexpr int MOE_MAX = MGX_MOE_MAX_EXPERTS;
+constexpr int MOE_REC = MGX_MOE_RECORD_WORDS;  // the record's words; [2e], [2e + 1] = start, count of expert e
+constexpr int MOE_REC_TILES = 16, MOE_REC_UNROUTABLE = 17, MOE_REC_CTR = 18;
+struct PolMoeArgs {
+    SampleAddr s;                          // the caller's index and n_samples
+    const uint8_t *newest;
+    const float *blob[MOE_MAX], *mfeat[MOE_MAX];
+    const uint8_t *route;                  // [256]
+    int n_experts, mode;
+    uint64_t seed;
+    unsigned long long *ctr;
+    int *rec;                              // [MOE_REC]
+    int64_t *list;                         // [n_samples + 63 n_experts]: SampleAddr.index of launch 2
+    int *pos;                              // the same length: the position p of each list entry
+    long long *actions;
+    float *values, *log_probs, *logits;
+};
+
+// Launch 1: a stable partition of the positions by expert, by ONE workgroup (mgx_boot_list_kernel's compaction, once
+// per expert).  Pass 1 counts every expert's samples (per wave, in registers) and lays the segments out; pass 2 places
+// the entries: per chunk of MOE_THREADS positions a ballot per expert and wave, the wave totals in LDS (two buffers
+// by chunk parity, so the running segment cursors are updated without a third barrier).  The expert of a position is
+// route[mids[index[p]]]: stack_slot's newest slot reads mids[index[p]] with and without terminal rows.
+constexpr int MOE_THREADS = 1024;
+__global__ __launch_bounds__(MOE_THREADS) void mgx_moe_route_kernel(PolMoeArgs a) {
+    constexpr int NWV = MOE_THREADS / 64;
+    __shared__ int s_tot[2][NWV][MOE_MAX + 1];                        // [.][.][MOE_MAX]: unroutable (pass 1 only)
+    __shared__ int s_cur[MOE_MAX];                                    // next free list slot of every expert
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t n = a.s.B;
+    const int E = a.n_experts;
+    // mode 2: this launch owns the counter: the snapshot is what every draw of launch 2 uses
+    if (tid == 0) {
+        unsigned long long c = 0;
+        if (a.mode == 2) {
+            c = *reinterpret_cast<volatile unsigned long long *>(a.ctr);
+            *reinterpret_cast<volatile unsigned long long *>(a.ctr) = c + 1ull;
+        }
+        a.rec[MOE_REC_CTR] = (int)(uint32_t)c;
+        a.rec[MOE_REC_CTR + 1] = (int)(uint32_t)(c >> 32);
+    }
+    if (tid >= MOE_REC_CTR + 2 && tid < MOE_REC) a.rec[tid] = 0;
+    // ---- pass 1: counts (wave-uniform registers: a ballot's popcount per expert)
+    int cnt[MOE_MAX + 1];
+#pragma unroll
+    for (int x = 0; x <= MOE_MAX; x++) cnt[x] = 0;
+    for (int64_t p0 = 0; p0 < n; p0 += MOE_THREADS) {
+        const int64_t p = p0 + tid;
+        const int e = p < n ? (int)a.route[a.s.mids[a.s.index[p]]] : -1;
+#pragma unroll
+        for (int x = 0; x < MOE_MAX; x++) cnt[x] += __popcll(__ballot(e == x && x < E));
+        cnt[MOE_MAX] += __popcll(__ballot(e >= E));
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int x = 0; x <= MOE_MAX; x++) s_tot[0][wv][x] = cnt[x];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int start = 0, tiles = 0;
+        for (int x = 0; x < MOE_MAX; x++) {
+            int c = 0;
+            for (int w = 0; w < NWV; w++) c += s_tot[0][w][x];
+            a.rec[2 * x] = start;
+            a.rec[2 * x + 1] = c;
+            s_cur[x] = start;
+            const int t = (c + POL_TILE - 1) / POL_TILE;
+            tiles += t;
+            start += t * POL_TILE;
+        }
+        int bad = 0;
+        for (int w = 0; w < NWV; w++) bad += s_tot[0][w][MOE_MAX];
+        a.rec[MOE_REC_TILES] = tiles;
+        a.rec[MOE_REC_UNROUTABLE] = bad;
+    }
+    __syncthreads();
+    // ---- pass 2: placement.  Slots stay below n + 63 E: segment e ends at start_e + count_e <= the padded total
+    int par = 1;                                                      // (buffer 0 was read by thread 0 above)
+    for (int64_t p0 = 0; p0 < n; p0 += MOE_THREADS, par ^= 1) {
+        const int64_t p = p0 + tid;
+        int64_t idx = 0;
+        int e = -1;
+        if (p < n) {
+            idx = a.s.index[p];
+            e = (int)a.route[a.s.mids[idx]];
+        }
+        const bool sel = e >= 0 && e < E;
+        unsigned long long mine = 0;
+#pragma unroll
+        for (int x = 0; x < MOE_MAX; x++) {
+            const unsigned long long m = __ballot(sel && e == x);
+            if (e == x) mine = m;
+            if (lane == x) s_tot[par][wv][x] = __popcll(m);
+        }
+        __syncthreads();
+        if (sel) {
+            int before = 0;
+            for (int w = 0; w < wv; w++) before += s_tot[par][w][e];
+            const int slot = s_cur[e] + before + __popcll(mine & ((1ull << lane) - 1ull));
+            a.list[slot] = idx;
+            a.pos[slot] = (int)p;
+        }
+        __syncthreads();                                              // s_cur was read by everyone
+        if (tid < MOE_MAX) {
+            int total = 0;
+            for (int w = 0; w < NWV; w++) total += s_tot[par][w][tid];
+            s_cur[tid] += total;                                      // read next after the next chunk's first barrier
+        }
+    }
+}
+
+// Launch 2: the policy pass over the partition.  Tile t of the lists (entries 64 t .. 64 t + 63) belongs to the expert
+// whose segment holds it; a segment starts at a multiple of 64, so no tile has two experts.  The live tiles number
+// sum_e ceil(c_e / 64) <= sum_e (c_e + 63) / 64 <= (n_samples + 63 E) / 64, rounded down because the left side is an
+// integer: that is the grid.  A workgroup past the live tile count exits after that one load.  One tile per
+// workgroup, as mgx_policy_kernel.
+template <int K>
+__global__ __launch_bounds__(POL_THREADS, 4) void mgx_policy_moe_kernel(PolMoeArgs a) {
+    extern __shared__ __align__(16) uint8_t smem[];
+    constexpr int LS = POL_LS;
+    float *X = reinterpret_cast<float *>(smem);                       // [pol_x_rows][65]
+    float *P = X + pol_x_rows(K) * LS;                                // [144][65]
+    float *F = P;
+    __shared__ const uint8_t *s_src[POL_TILE * K];
+    __shared__ int s_mid[POL_TILE * K];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tile = (int)blockIdx.x;
+    if (tile >= a.rec[MOE_REC_TILES]) return;                         // the whole workgroup: no barrier is skipped
+    int e = 0, nb = 0;
+    for (int x = 0; x < a.n_experts; x++) {                           // <= 8 records; exactly one holds a live tile
+        const int t0 = a.rec[2 * x] / POL_TILE, c = a.rec[2 * x + 1];
+        if (tile >= t0 && (tile - t0) * POL_TILE < c) {
+            e = x;
+            nb = min(POL_TILE, c - (tile - t0) * POL_TILE);
+        }
+    }
+    e = __builtin_amdgcn_readfirstlane(e);                            // wave-uniform: weight addresses stay scalar
+    nb = __builtin_amdgcn_readfirstlane(nb);
+    const float *__restrict__ W = a.blob[e];
+    const int64_t b0 = (int64_t)tile * POL_TILE;                      // the tile's first list slot
+    const SampleAddr s{a.s.rows, a.s.mids, a.s.starts, a.s.N, a.s.R, a.list, b0 + nb};
+    pol_stage_src<K>(s, a.newest, b0, nb, tid, s_src, s_mid);         // A
+    __syncthreads();
+    pol_stage_rows<K>(s_src, tid, X);                                 // A2
+    int v;
+    const float *__restrict__ mf = a.mfeat[e] + (size_t)pol_feat_row<K>(s_mid, lane, nb, v) * 128;
+    __syncthreads();
+    const uint8_t *xb = reinterpret_cast<const uint8_t *>(X) + lane * 4;
+    const uint32_t dsel = pol_dsel<K>(xb);
+    pol_conv1<K>(W, wv, lane, xb, P);                                 // B
+    __syncthreads();
+    pol_conv2<K>(W, wv, lane, P, X);                                  // C
+    __syncthreads();
+    pol_conv3_dir<K>(W, wv, lane, dsel, v, X, F);                     // D
+    __syncthreads();
+    pol_l0<K>(W, wv, lane, mf, F, X);                                 // E
+    __syncthreads();
+    pol_l1<K>(W, wv, lane, X, P);                                     // F
+    __syncthreads();
+    if (wv != 0) return;                                              // G: wave 0; outputs and the draw's key at p
+    const int64_t p = lane < nb ? a.pos[b0 + lane] : 0;
+    pol_heads<K>(W, P, lane, lane < nb, p, a.mode, a.seed,
+                 [&] { return *reinterpret_cast<const unsigned long long *>(a.rec + MOE_REC_CTR); }, a.actions,
+                 a.values, a.log_probs, a.logits);
 }
 
 #endif  // MGX_POLICY_H_

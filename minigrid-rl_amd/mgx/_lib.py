@@ -32,8 +32,10 @@ EXPORTS = ("mgx_last_error", "mgx_abi_version", "mgx_create", "mgx_destroy", "mg
            "mgx_mission_workspace_words", "mgx_mission_forward", "mgx_mission_backward",
            "mgx_ppo_loss_scratch_words", "mgx_ppo_loss", "mgx_adam_scratch_words", "mgx_adam_step",
            "mgx_mission_forward_rows", "mgx_mission_backward_rows", "mgx_adam_schedule", "mgx_adam_step_sched",
-           "mgx_eval_record")
+           "mgx_eval_record", "mgx_policy_moe_scratch_words", "mgx_policy_act_moe")
 CLOCK_CLASSES = 4   # == MGX_CLOCK_CLASSES (include/mgx.h)
+MOE_MAX_EXPERTS = 8     # == MGX_MOE_MAX_EXPERTS (include/mgx.h)
+MOE_RECORD_WORDS = 32   # == MGX_MOE_RECORD_WORDS (include/mgx.h)
 
 
 class MgxConfig(ctypes.Structure):
@@ -100,6 +102,15 @@ class MgxActOut(ctypes.Structure):
     _fields_ = [
         ("actions_dev", ctypes.c_void_p), ("values_dev", ctypes.c_void_p), ("log_probs_dev", ctypes.c_void_p),
         ("logits_dev", ctypes.c_void_p),
+    ]
+
+
+class MgxPolicyMoe(ctypes.Structure):
+    _fields_ = [
+        ("n_experts", ctypes.c_int32), ("mode", ctypes.c_int32),
+        ("blob_dev", ctypes.c_void_p * MOE_MAX_EXPERTS), ("mission_feat_dev", ctypes.c_void_p * MOE_MAX_EXPERTS),
+        ("route_dev", ctypes.c_void_p), ("seed", ctypes.c_uint64), ("counter_dev", ctypes.c_void_p),
+        ("scratch_dev", ctypes.c_void_p), ("scratch_words", ctypes.c_int64),
     ]
 
 
@@ -208,6 +219,10 @@ def load():
     L.mgx_policy_act.argtypes = [P, P, P, P, I64, I64, P, I64, P, ctypes.POINTER(MgxPolicy), ctypes.POINTER(MgxActOut), P]
     L.mgx_policy_bootstrap.argtypes = [P, P, P, P, I64, I64, I64, P, ctypes.POINTER(MgxPolicy),
                                        ctypes.POINTER(MgxBootstrap), P]
+    L.mgx_policy_moe_scratch_words.argtypes = [I64, I]
+    L.mgx_policy_moe_scratch_words.restype = I64
+    L.mgx_policy_act_moe.argtypes = [P, P, P, P, I64, I64, P, I64, P, ctypes.POINTER(MgxPolicyMoe),
+                                     ctypes.POINTER(MgxActOut), P]
     L.mgx_policy_grad_scratch_words.argtypes = [I, I64, I]
     L.mgx_policy_grad_scratch_words.restype = I64
     L.mgx_policy_backward.argtypes = [P, P, P, P, I64, I64, P, I64, ctypes.POINTER(MgxPolicyGrad), P]
