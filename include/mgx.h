@@ -71,7 +71,9 @@ typedef struct mgx_config {
     int32_t problem;           /* mgx_problem; `env.problem` */
     int32_t mission;           /* `env.mission` (problem multi): 0 'go to', 1 'toggle', 2 'pick up',
                                   5 'go to goal'; -1 = None */
-    int32_t size;              /* `env.size` (5..16); max_steps = size^2 (custom_env.py:114) */
+    int32_t size;              /* `env.size` (5..16); max_steps = size^2 (custom_env.py:114).  Problem multi
+                                  needs 6..16: at 5 the reference's goal placement in a 4-room layout never
+                                  ends (every free cell is next to a door), so mgx_create refuses it */
     int32_t num_objects;       /* `env.num_objects` */
     int32_t see_through_walls; /* `env.see_through_walls`; 0 = minigrid Grid.process_vis occlusion */
     int32_t all_doors_open;    /* `env.all_doors_open` */

@@ -88,7 +88,7 @@ struct MtCtl {
 };
 // (MT_SB_WORDS, MT_SB_GROUPS, MT_SLIDE_MAX_SB: mgx_device.h, with the slide's arithmetic)
 constexpr unsigned long long MT_AHEAD = 1ull << 19;       // words kept generated past the furthest producer cursor
-constexpr long long MT_HOST_FILL = 1ll << 20;             // words the host generates at create
+constexpr long long MT_HOST_FILL = 1ll << 20;             // words the host generates at create, at least (mgx_create)
 // 256 threads: the slider must find room on a CU beside the step / rollout kernels (a 1,024-thread
 // workgroup waited ~50 us for a whole CU behind the fused rollout, and the refill waited behind it)
 constexpr int SLIDE_THREADS = 256, SLIDE_ENVS = 16 * SLIDE_THREADS;
@@ -2915,6 +2915,11 @@ static mgx_status validate(const mgx_config *c) {
             if (!(c->mission == -1 || c->mission == 0 || c->mission == 1 || c->mission == 2 || c->mission == 5))
                 return fail(MGX_ERR_INVALID, "multi: mission must be None, 0, 1, 2 or 5");
             if (c->num_objects > 18) return fail(MGX_ERR_INVALID, "Number of objects to be generated is more than the available objects.");
+            // 5x5: a 4-room layout leaves four interior cells, each next to a door, so
+            // _generate_4_rooms' place_obj(Goal()) rejects every cell (custom_env.py:1394-1401)
+            if (c->size == 5)
+                return fail(MGX_ERR_INVALID, "multi needs size >= 6 (at size 5 the reference's goal placement "
+                                             "in a 4-room layout never ends: every free cell is next to a door)");
             break;
         case MGX_PROBLEM_GTO: case MGX_PROBLEM_GTG:
             if (c->num_objects > 24) return fail(MGX_ERR_INVALID, "Number of objects to be generated is more than the available objects.");
@@ -3000,8 +3005,14 @@ mgx_status mgx_create(const mgx_config *cfg, int device, mgx_handle **out) {
     const int S = cfg->size;
     const int GS = ((S * S) + 15) & ~15;
     const int IMG = FRAME * cfg->n_stack;
-    // initial fill: whole super-blocks, MT_HOST_FILL words at most (the slider generates the rest)
-    const int64_t hi0 = std::min(ring_groups * MT_FIELDS, (int64_t)MT_HOST_FILL) / MT_SB_WORDS * MT_SB_GROUPS;
+    // initial fill: whole super-blocks (the slider generates the rest).  No slide runs between mgx_create and the
+    // first mgx_reset's ring fill, which budgets ring_depth ATTEMPTS per lane, each up to livelock_words words: on a
+    // small multi grid half of them are abandoned at that many (6x6: 1.09 M words per lane on average at the
+    // default depth, more than MT_HOST_FILL -- the lanes then read past the stream, MGX_DEVERR_MT_TABLE), so the
+    // host generates what such a fill can take plus the slider's usual lead
+    const int64_t fill_words = std::max((int64_t)MT_HOST_FILL,
+                                        (int64_t)h->cfg.ring_depth * h->cfg.livelock_words + (int64_t)MT_AHEAD);
+    const int64_t hi0 = std::min(ring_groups * MT_FIELDS, fill_words) / MT_SB_WORDS * MT_SB_GROUPS;
 
     auto bail = [&](mgx_status st) {
         for (void *&p : h->allocs) if (p) { (void)hipFree(p); p = nullptr; }

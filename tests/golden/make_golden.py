@@ -327,12 +327,27 @@ CONFIGS += [
     ("manual_multi_all_s8", dict(problem="multi", mission=None, size=8, manual=True)),
     ("manual_multi_pkp_s11", dict(problem="multi", mission=2, size=11, manual=True)),
 ]
+# every other size mgx_create accepts (5..16): the size selects the engine's kernel instantiation
+# (words per occupancy mask, the constant-size 8x8 kernels, the 32-env blocks at 16).
+# At 6 and 7 abandoned reset attempts are the common case; at 5 and 6 the 7x7 view is wider than the
+# grid.  multi at 5 is refused (the reference's goal placement never ends), so 5 is a single room.
+for S in (6, 7, 9, 10, 12, 13, 14, 15):
+    CONFIGS.append(("multi_all_s%d" % S, dict(problem="multi", mission=None, size=S)))
+CONFIGS += [
+    ("single_gtg_s5", dict(problem="gtg", mission=None, size=5, num_objects=2)),
+    ("single_mov_s6", dict(problem="mov", mission=None, size=6)),
+    ("single_pkp_s7", dict(problem="pkp", mission=None, size=7)),
+    ("novis_multi_all_s6", dict(problem="multi", mission=None, size=6, see_through_walls=False)),
+    ("obst_multi_all_s13", dict(problem="multi", mission=None, size=13, obstacles=True)),
+    ("ado_multi_all_s10", dict(problem="multi", mission=None, size=10, all_doors_open=True)),
+]
 
 
 # the configs --agent scripted runs (written as deep_<name>.npz)
 DEEP = ("multi_all_s8", "obst_multi_all_s8", "novis_multi_all_s8", "ado_multi_all_s8", "manual_multi_all_s8",
         "multi_pkp_s11", "multi_all_s11_o8", "multi_tgl_s16", "multi_gtg_s16", "novis_obst_multi_tgl_s16",
-        "single_full_s8", "single_mov_s8", "single_drp_s8", "single_opn_s8")
+        "single_full_s8", "single_mov_s8", "single_drp_s8", "single_opn_s8",
+        "multi_all_s7", "multi_all_s13")
 
 
 def main():

@@ -54,7 +54,10 @@ def test_invalid_configs_rejected_without_gpu(lib):
            # room too small for everything place_obj must place: the reference never returns
            dict(problem=P["full"], size=7), dict(problem=P["gtg"], size=5, num_objects=8),
            dict(problem=P["mov"], size=5, num_objects=7, obstacles=1, percent_obstacles=0.3),
-           dict(problem=P["drp"], num_objects=25)]
+           dict(problem=P["drp"], num_objects=25),
+           # multi on 5x5: a 4-room layout's four free cells are all next to a door, so the reference's goal
+           # placement never ends (tests/test_generator_host.py shows the generator's error bit)
+           dict(size=5), dict(size=5, mission=-1), dict(size=5, mission=2, all_doors_open=1)]
     for kw in bad:
         c = _lib.MgxConfig(problem=0, mission=5, size=8, num_objects=4, see_through_walls=1, n_stack=4,
                            n_envs=64, base_seed=42)

@@ -52,6 +52,12 @@ CASES = [("multi", 5, 8, 0, 0), ("multi", None, 8, 0, 0), ("multi", 1, 16, 0, 0)
          ("multi", None, 8, 1, 0), ("multi", 0, 16, 1, 0), ("multi", None, 11, 0, 0), ("pkp", None, 8, 0, 0),
          ("gtg", None, 8, 0, 0), ("multi", None, 8, 0, 4), ("gtg", None, 8, 0, 1), ("mov", None, 8, 0, 2),
          ("full", None, 11, 0, 0), ("pkp", None, 11, 0, 3), ("opn", None, 16, 0, 0)]
+# every other size mgx_create accepts: multi at each size it accepts (abandoned attempts are the common
+# case at 6 and 7), open doors at one size per occupancy-mask width, single rooms from 5 up
+CASES += [("multi", None, S, 0, 0) for S in (6, 7, 9, 10, 12, 13, 14, 15)]
+CASES += [("multi", 2, 6, 1, 0), ("multi", 2, 10, 1, 0), ("multi", 2, 13, 1, 0), ("gtg", None, 5, 0, 0),
+          ("pkp", None, 7, 0, 0), ("mov", None, 7, 0, 2), ("full", None, 9, 0, 0), ("full", None, 13, 0, 0),
+          ("opn", None, 15, 0, 0)]
 
 
 @pytest.mark.parametrize("problem,mission,size,ado,nobst", CASES,
@@ -90,3 +96,16 @@ def test_host_generator_matches_oracle(problem, mission, size, ado, nobst):
         assert np.array_equal(ll[:, k], r["livelock"] if k == 0 else o["livelock"]), ("livelock", k)
         o = ov.step(np.full(n, 6, np.int32))                  # 'done': ends every episode, auto-reset
         assert (o["terminated"] | o["truncated"]).all()
+
+
+def test_multi_at_size_5_never_places_its_goal():
+    """Why mgx_create refuses multi at size 5: a 4-room layout leaves four interior cells, every one next to
+    a door, so the goal's placement rejects them all (the reference loops for ever in _generate_4_rooms'
+    place_obj(Goal()), custom_env.py:1394-1401).  The generator's PCG64 safety bound ends the stuck envs
+    and reports MGX_DEVERR_PCG_LOOP."""
+    n, E, S = 4, 6, 5
+    L = _lib()
+    bufs = [np.zeros((n, E, S * S), np.uint8), np.zeros((n, E, 3), np.uint8), np.zeros((n, E, 4), np.uint8),
+            np.zeros((n, E), np.int64), np.zeros((n, E, 4), np.uint64), np.zeros((n, E), np.int32)]
+    err = L.hg_run(PROBLEMS["multi"], -1, S, 4, 0, 0, n, 42, E, *[_p(b) for b in bufs])
+    assert err & 4, err

@@ -127,10 +127,11 @@ FIXTURES = TC.fixtures()
 @pytest.mark.parametrize("kw", [dict(problem="full", size=7), dict(problem="gtg", size=5, num_objects=8),
                                 dict(problem="mov", size=5, num_objects=7, obstacles=True, percent_obstacles=0.3),
                                 dict(problem="multi", mission=3), dict(problem="opn", num_objects=13),
-                                dict(problem="nope")])
+                                dict(problem="nope"), dict(problem="multi", mission=None, size=5)])
 def test_unsatisfiable_or_invalid_configs_are_rejected(kw):
     """Configs on which the reference raises (ValueError / AssertionError) or never returns
-    (place_obj over a room with too few free cells) are refused at create time."""
+    (place_obj over a room with too few free cells; multi's goal on a 5x5 grid of four rooms, where
+    every free cell is next to a door) are refused at create time."""
     _need_gpu()
     from mgx import MgxEngine
     from mgx._lib import MgxError
@@ -155,7 +156,10 @@ def test_engine_matches_reference_fixture(path, layout):
 
 @pytest.mark.parametrize("name", ["multi_all_s8", "multi_gtg_s8", "multi_tgl_s16", "single_pkp_s8",
                                   "single_full_s8", "obst_single_mov_s11", "novis_obst_multi_tgl_s16",
-                                  "ado_multi_all_s11"])
+                                  "ado_multi_all_s11",
+                                  # one size per occupancy-mask width outside 8 / 11 / 16 (generic kernels; at 6 about
+                                  # every second attempt is abandoned, inline and in the refill)
+                                  "multi_all_s6", "multi_all_s10", "multi_all_s13"])
 @pytest.mark.parametrize("ring", [(-1, 0, "sb3"), (2, 1, "sb3"), (4, 2, "sb3"), (8, 3, "sb3"), (2, 1, "compact"),
                                   (8, 3, "compact")],
                          ids=["inline", "ring2", "ring4", "ring8_every3", "compact_ring2", "compact_ring8_every3"])
@@ -183,7 +187,11 @@ def test_engine_reset_paths_match_fixture(name, ring):
                                               # at 8 is the largest grid LDS beside the largest stack area
                                               ("multi_pkp_s11", 5, "i64"), ("novis_single_gto_s11", 5, "u8"),
                                               ("multi_all_s8", 6, "u8"), ("novis_multi_all_s8", 7, "i64"),
-                                              ("multi_gtg_s8", 8, "u8"), ("multi_tgl_s16", 8, "i64")])
+                                              ("multi_gtg_s8", 8, "u8"), ("multi_tgl_s16", 8, "i64"),
+                                              # the view wider than the grid (with and without occlusion), and the
+                                              # generic 4-word kernels
+                                              ("multi_all_s6", 4, "u8"), ("novis_multi_all_s6", 3, "i64"),
+                                              ("multi_all_s13", 8, "i64")])
 def test_frame_stack_and_terminal_obs_match_sb3_layer(name, n_stack, mdt):
     """Full stacked observation + stacked terminal_observation every step vs the
     numpy VecTransposeImage/VecFrameStack restatement fed with the fixture."""
@@ -255,6 +263,57 @@ def test_engine_matches_oracle_1024_envs(problem, mission, size, ado):
         assert np.array_equal(np.where(done, tdr, dr), o["dir"]), t
         assert np.array_equal(np.where(done[:, None], tmi, mi), o["mission"]), t
         assert np.array_equal(eng.livelock.cpu().numpy()[done], o["livelock"][done]), t
+    a, b = eng.dump_state(), ov.dump()
+    for k in ("grid", "agent", "carrying", "step_count", "mission_done", "mtwords", "pcg", "target"):
+        assert np.array_equal(a[k], b[k]), k
+    assert np.array_equal(a["stored_reward"], b["stored_reward"], equal_nan=True)
+    eng.poll_error()
+
+
+SIZE_SWEEP = [("multi", None, S, 4) for S in (6, 7, 9, 10, 12, 13, 14, 15)] + [("gtg", None, S, 2) for S in (5, 6, 7)]
+
+
+@pytest.mark.parametrize("problem,mission,size,nobj", SIZE_SWEEP, ids=["%s_s%d" % (c[0], c[2]) for c in SIZE_SWEEP])
+def test_engine_matches_oracle_at_every_size(problem, mission, size, nobj):
+    """The sizes between the ones everything else runs at (8, 11, 16).  The size picks the kernels: S*S <= 64 the
+    one-word occupancy masks (the generic instantiations, not the constant-size 8x8 ones), <= 128 two words, else
+    four; at 5 and 6 the 7x7 view is wider than the grid, at 6 and 7 abandoned reset attempts are
+    common.  200 envs (three full workgroups and a tail of 8) x 96 random steps, sharded seeding, bit-exact vs the
+    C oracle: flags, both rewards, the frame (the terminal one where done), the new episode's frame, the mission,
+    the abandoned-attempt counts, and every field of the final state."""
+    _need_gpu()
+    import oracle as O
+    from mgx import MgxEngine
+    n, T, off = 200, 96, 4096
+    ov = O.OracleVec(problem, mission, size, nobj, n, 42, index_offset=off)
+    eng = MgxEngine(problem=problem, mission=mission, size=size, num_objects=nobj, n_envs=n, env_index_offset=off,
+                    n_stack=4, terminal_mode="all", reward64=True)
+    r = ov.reset()
+    obs = eng.reset()
+    img, dr, mi = EngineSource.newest(obs)
+    assert np.array_equal(img, r["image"]) and np.array_equal(dr, r["dir"]) and np.array_equal(mi, r["mission"])
+    assert np.array_equal(eng.livelock.cpu().numpy(), r["livelock"])
+    acts = np.random.default_rng(99).integers(0, 7, (T, n))
+    n_done = 0
+    for t in range(T):
+        o = ov.step(acts[t])
+        obs = eng.step(torch.as_tensor(acts[t], device=eng.device))
+        done = eng.done.cpu().numpy().astype(bool)
+        n_done += int(done.sum())
+        assert np.array_equal(done, (o["terminated"] | o["truncated"]).astype(bool)), t
+        assert np.array_equal(eng.terminated.cpu().numpy(), o["terminated"].astype(bool)), t
+        assert np.array_equal(eng.reward64.cpu().numpy(), o["reward"]), t
+        assert np.array_equal(eng.reward.cpu().numpy(), o["reward"].astype(np.float32)), t
+        img, dr, mi = EngineSource.newest(obs)
+        timg, tdr, tmi = EngineSource.newest(eng.terminal_obs)
+        assert np.array_equal(np.where(done[:, None, None, None], timg, img), o["image"]), t
+        assert np.array_equal(img[done], o["r_image"][done]), t
+        assert np.array_equal(dr[done], o["r_dir"][done]), t
+        assert np.array_equal(np.where(done, tdr, dr), o["dir"]), t
+        assert np.array_equal(np.where(done[:, None], tmi, mi), o["mission"]), t
+        assert np.array_equal(mi[done], o["r_mission"][done]), t
+        assert np.array_equal(eng.livelock.cpu().numpy()[done], o["livelock"][done]), t
+    assert n_done > n                                  # (a condition on the inputs: every path above was compared)
     a, b = eng.dump_state(), ov.dump()
     for k in ("grid", "agent", "carrying", "step_count", "mission_done", "mtwords", "pcg", "target"):
         assert np.array_equal(a[k], b[k]), k
@@ -544,6 +603,38 @@ def test_refill_accounting():
     eng.poll_error()
 
 
+def test_refill_accounting_with_abandoned_attempts():
+    """test_refill_accounting's invariants at multi 6x6, where every second reset attempt is abandoned (the
+    reference fixture multi_all_s6: 1,268 abandoned attempts for 1,249 resets): mgx_reset's fill budgets D ATTEMPTS
+    per lane, so it leaves the rings about half full, and never below the floor of 2K; over 10 epochs of random
+    actions every ring holds between K and D episodes at each epoch's end, and the episodes produced are the resets
+    consumed plus the change of the queue (never negative: nothing is lost)."""
+    _need_gpu()
+    from mgx import MgxEngine
+    n = 4096
+    eng = MgxEngine(problem="multi", mission=None, size=6, n_envs=n, terminal_mode="none")
+    eng.reset()
+    K, D = eng.refill_every, eng.ring_depth
+    st = eng.stats()
+    lv = eng.ring_levels()
+    assert 2 * K * n <= st["queued"] <= D * n and st["refill_launches"] == 1 and st["calls"] == 0, st
+    assert lv.min() >= 2 * K and lv.max() <= D and int(lv.astype(np.int64).sum()) == st["queued"], (lv.min(), lv.max())
+    g = torch.Generator(device="cuda")
+    g.manual_seed(5)
+    for epoch in range(10):
+        prev = st
+        for _ in range(K):
+            eng.step(torch.randint(0, 7, (n,), device="cuda", generator=g, dtype=torch.int32))
+        st = eng.stats()
+        lv = eng.ring_levels()
+        assert n * K <= st["queued"] <= n * D, (epoch, st)
+        assert lv.min() >= K and lv.max() <= D, (epoch, lv.min(), lv.max())     # (include/mgx.h: refill_every)
+        produced = (st["resets"] - prev["resets"]) + (st["queued"] - prev["queued"])
+        assert produced >= 0 and st["resets"] - prev["resets"] > 0, (epoch, st, prev)
+        assert st["refill_launches"] == 2 + epoch and st["calls"] == K * (epoch + 1)
+    eng.poll_error()
+
+
 def _full_stacks_vs_oracle(n, n_stack, terminal_mode, T=160, **engine_kw):
     """multi 8x8, n envs, T random steps: the full stacked observation and the stacked terminal_observation of
     every step against the C oracle + the numpy VecFrameStack restatement."""
@@ -606,17 +697,21 @@ def test_inline_reset_full_stacks_at_n_stack_8():
     assert eng.ring_depth == 0                       # the engine did run without a ring
 
 
-@pytest.mark.parametrize("ring", [(0, 0, 0), (16, 4, 1), (8, 4, -1)], ids=["default", "d16_k4_cap1", "d8_k4_fill"])
-def test_ring_never_runs_dry_under_max_consumption(ring):
+@pytest.mark.parametrize("size,ring", [(8, (0, 0, 0)), (8, (16, 4, 1)), (8, (8, 4, -1)), (6, (0, 0, 0)), (7, (0, 0, 0))],
+                         ids=["default", "d16_k4_cap1", "d8_k4_fill", "s6_default", "s7_default"])
+def test_ring_never_runs_dry_under_max_consumption(size, ring):
     """Every env resets every step ('done' action: one episode per step, the most a
     step can consume) -- the refill's production rule must keep every ring non-empty
-    (no MGX_DEVERR_RING_EMPTY) and the stream must stay bit-exact with the oracle."""
+    (no MGX_DEVERR_RING_EMPTY) and the stream must stay bit-exact with the oracle.  At 6x6 every second reset
+    attempt is abandoned (4,096 MT words each) and at 7x7 one in ten: an abandoned attempt takes one of the
+    epoch's attempts from its lane unless the ring's floor needs it, and the ring's first fill alone reads past
+    the first 2^20 words of the stream on most lanes (no MGX_DEVERR_MT_TABLE)."""
     _need_gpu()
     import oracle as O
     from mgx import MgxEngine
     n, T = 512, 160
-    ov = O.OracleVec("multi", None, 8, 4, n, 42)
-    eng = MgxEngine(problem="multi", mission=None, size=8, n_envs=n, terminal_mode="none",
+    ov = O.OracleVec("multi", None, size, 4, n, 42)
+    eng = MgxEngine(problem="multi", mission=None, size=size, n_envs=n, terminal_mode="none",
                     ring_depth=ring[0], refill_every=ring[1], refill_cap=ring[2])
     ov.reset()
     eng.reset()
@@ -634,8 +729,8 @@ def test_ring_never_runs_dry_under_max_consumption(ring):
         assert np.array_equal(a_[k], b_[k]), k
 
 
-@pytest.mark.parametrize("ring_depth", [0, -1], ids=["ring", "inline"])
-def test_mt_stream_outlives_its_ring(ring_depth):
+@pytest.mark.parametrize("ring_depth,size", [(0, 8), (-1, 8), (16, 6)], ids=["ring", "inline", "ring_s6"])
+def test_mt_stream_outlives_its_ring(ring_depth, size):
     """The shared MT19937(42) stream (custom_env.py:82, one CPython `random` per env) never runs
     out: the device holds a ring of it (mt_table_words = 2^18 -> 32,768 groups = 327,680 words) and
     mgx_mt_slide_kernel keeps generating the stream on the device ahead of the furthest cursor,
@@ -644,16 +739,28 @@ def test_mt_stream_outlives_its_ring(ring_depth):
     must hold), with an unseeded VecEnv.reset() in the middle (both streams continue from each
     env's current episode, so its cursor must still be in the ring): transitions bit-exact vs the
     C oracle (per-env CPython MT state), every RNG position equal at the end, no
-    MGX_DEVERR_MT_TABLE."""
+    MGX_DEVERR_MT_TABLE.
+
+    ring_s6: multi (every mission) 6x6, 256 envs.  Every second reset attempt is abandoned at 4,096 words, so the
+    stream runs ~20 times faster per step than at 8x8 and the cursors drift apart as fast: measured on the C oracle
+    alone (same actions), they spread over 383 k words by the time the stream is two lengths of the 2^18-word ring
+    (step 700) -- more than that ring holds, and this test's last assertion fails on the oracle's own cursors.  So
+    the ring is the next size that holds the spread while two of its lengths are generated (2^20 words -> 131,072
+    groups; the spread grows like sqrt(steps), ~850 k words at step 3,600), with 16 episodes queued per env (the
+    producers run ahead of the oldest live cursor by the queue as well: ~70 k words at 16, 2.4 M at the default
+    512), and T is where the ORACLE's furthest cursor has passed two ring lengths (asserted below)."""
     _need_gpu()
     import oracle as O
     from mgx import MgxEngine
-    n = 1024
-    T = 48000 if ring_depth == 0 else 24000
-    ov = O.OracleVec("multi", 5, 8, 4, n, 42)
-    eng = MgxEngine(problem="multi", mission=5, size=8, n_envs=n, n_stack=4, terminal_mode="none", reward64=True,
-                    mt_table_words=1 << 18, ring_depth=ring_depth)
-    ring_words = 32768 * 10
+    if size == 8:
+        n, mission, table, ring_groups = 1024, 5, 1 << 18, 32768
+        T = 48000 if ring_depth == 0 else 24000
+    else:
+        n, mission, table, ring_groups, T = 256, None, 1 << 20, 131072, 3600
+    ov = O.OracleVec("multi", mission, size, 4, n, 42)
+    eng = MgxEngine(problem="multi", mission=mission, size=size, n_envs=n, n_stack=4, terminal_mode="none",
+                    reward64=True, mt_table_words=table, ring_depth=ring_depth)
+    ring_words = ring_groups * 10
     ov.reset()
     eng.reset()
     rng = np.random.default_rng(31)
@@ -680,7 +787,9 @@ def test_mt_stream_outlives_its_ring(ring_depth):
     for k in ("grid", "agent", "carrying", "step_count", "mission_done", "mtwords", "pcg", "target"):
         assert np.array_equal(a[k], b[k]), k
     st = eng.stats()
-    assert st["mt_generated"] > (2 if ring_depth == 0 else 1) * ring_words, st   # the ring was rewritten
+    if size != 8:
+        assert b["mtwords"].max() > 2 * ring_words, b["mtwords"].max()          # (the oracle's: T is long enough)
+    assert st["mt_generated"] > (2 if ring_depth >= 0 else 1) * ring_words, st   # the ring was rewritten
     assert a["mtwords"].max() - a["mtwords"].min() < ring_words
     if ring_depth == 0:
         # the refill finds the prefix records of a stream that has wrapped its ring (tests/test_prefix_records.py):

@@ -12,7 +12,19 @@ FIXTURES = TC.fixtures()
 
 
 def test_fixtures_present():
-    assert len(FIXTURES) == 53                    # 39 random-action runs + 14 scripted-agent (deep_*) runs
+    assert len(FIXTURES) == 69                    # 53 random-action runs + 16 scripted-agent (deep_*) runs
+
+
+def test_fixtures_pin_every_size():
+    """Every size mgx_create accepts has a reference fixture; multi (one kernel instantiation per
+    occupancy-mask width) has one at every size it accepts."""
+    sizes, multi = set(), set()
+    for p in FIXTURES:
+        d = np.load(p)
+        sizes.add(int(d["meta"][0]))
+        if str(d["problem"]) == "multi":
+            multi.add(int(d["meta"][0]))
+    assert sizes == set(range(5, 17)) and multi == set(range(6, 17)), (sizes, multi)
 
 
 def test_manual_fixtures_hold_premature_dones():
@@ -35,7 +47,8 @@ def test_oracle_matches_reference_fixture(path):
 
 
 def test_fixture_covers_quirks():
-    """The fixtures exercise the paths that matter.  Over the whole set: live-locks (S=8), truncation,
+    """The fixtures exercise the paths that matter.  Over the whole set: live-locks (S=8; multi_all_s6 and
+    multi_all_s7 each hold abandoned attempts of their own, the common case on small grids), truncation,
     mission completion with stored reward, goal termination.  Per scripted-agent fixture (deep_*,
     tests/golden/scripted_agent.py) floors on the deep-episode events of TC.events -- conditions on the
     inputs, not measurements of the code under test: the time limit reached at every size, locked doors
@@ -51,6 +64,8 @@ def test_fixture_covers_quirks():
         tot_trunc += int(d["truncated"].sum())
         tot_goal += int(((d["reward"] > 0) & (d["terminated"] == 1)).sum())
         tot_stored += int(np.isfinite(d["stored_reward"]).sum())
+        if name in ("multi_all_s6", "multi_all_s7"):
+            assert int(d["livelock"].sum() + d["reset0_livelock"].sum()) > 0, name
         if not name.startswith("deep_"):
             continue
         n_deep += 1
@@ -70,6 +85,6 @@ def test_fixture_covers_quirks():
         trunc_md_s16 += e["trunc_mission_done"] if S == 16 else 0
         wrong_key += e["wrong_key"]
     assert tot_ll > 0 and tot_goal > 0 and tot_stored > 0 and tot_trunc > 0
-    assert n_deep == 14
+    assert n_deep == 16
     assert trunc_md >= 50 and trunc_md_s16 >= 1, (trunc_md, trunc_md_s16)
     assert wrong_key >= 1

@@ -33,7 +33,8 @@ class Sim:
         self.look, self.fields, self.sbg, self.maxsb = (self.L.hg_const(k) for k in range(4))
         assert (self.look, self.fields, self.sbg * self.fields) == (320, 10, 3120)
         self.rg, self.rw, self.threads = ring_groups, ring_groups * self.fields, threads
-        # mgx_create: the host fills whole super-blocks of min(ring, 2^20 words), records for all but the last PFX_LOOK
+        # mgx_create: the host fills whole super-blocks of min(ring, 2^20 words) (more where ring_depth x livelock_words
+        # asks for it: the same state further up the stream), records for all but the last PFX_LOOK
         self.hi = min(self.rw, 1 << 20) // (self.sbg * self.fields) * self.sbg
         self.done = self.hi * self.fields - self.look
         self.slots = None

@@ -32,7 +32,13 @@ CASES = [dict(problem="multi", mission=5, size=8, n=4096),                     #
          dict(problem="multi", mission=1, size=16, n=130, see_through_walls=False),
          dict(problem="multi", mission=2, size=11, n=257, all_doors_open=True),
          dict(problem="mov", mission=None, size=8, n=200),                     # 'move' target ranges
-         dict(problem="multi", mission=None, size=8, n=512, manual=True)]
+         dict(problem="multi", mission=None, size=8, n=512, manual=True),
+         # the generic one-word-mask kernels (S*S <= 64 and S != 8; the view wider than the grid at 6)
+         dict(problem="multi", mission=None, size=6, n=200),
+         dict(problem="multi", mission=None, size=7, n=130, see_through_walls=False),
+         dict(problem="multi", mission=2, size=10, n=257),                     # two-word masks
+         dict(problem="multi", mission=None, size=13, n=200),                  # four-word masks in 64-env blocks
+         dict(problem="mov", mission=None, size=6, n=130)]
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "_".join("%s%s" % (k[:3], v) for k, v in c.items()))
@@ -273,6 +279,71 @@ def test_rollout_matches_reference_fixture(path):
             assert np.array_equal(st[k][done], d["r_" + k][t][done]), (t, k)
         assert np.array_equal(st["mission_done"], d["mission_done"][t]), t
         assert np.array_equal(st["stored_reward"], d["stored_reward"][t], equal_nan=True), t
+    eng.poll_error()
+
+
+@pytest.mark.parametrize("size", [6, 13])
+def test_rollout_gae_matches_oracle_at_generic_sizes(size):
+    """mgx_rollout_compact_gae (the GAE folded into the rollout launch) in the generic rollout kernels: 6x6 (one-word
+    masks, not the constant-size 8x8 kernel) and 13x13 (four-word masks in 64-env blocks; 16x16 runs 32-env blocks).
+    200 envs (a ragged last block), three 32-step epochs of random actions, random f32 values: every step's row,
+    mission id, done flag and f32 reward against the C oracle, the advantages and returns of every launch equal to
+    the numpy GAE fed the oracle's rewards and dones, (sum A, sum A^2, n) within fp64 summation error; every env's
+    state at the end."""
+    _need_gpu()
+    import oracle as O
+    from mgx import MgxEngine
+    from mgx._lib import mission_tokens
+    from mgx.compact import CompactBuffer
+    n, E, T = 200, 32, 96
+    ov = O.OracleVec("multi", None, size, 4, n, 42)
+    eng = MgxEngine(problem="multi", mission=None, size=size, n_envs=n, terminal_mode="truncated",
+                    mission_dtype=torch.uint8, refill_every=E)
+    assert eng.refill_every == E
+    buf = CompactBuffer(eng, T)
+    tok = mission_tokens()
+    ov.reset()
+    eng.reset()
+    buf.observe(0)
+    H = buf.H
+    rng = np.random.default_rng(size)
+    acts = rng.integers(0, 7, (T, n)).astype(np.int32)
+    vals = rng.standard_normal((T + 1, n)).astype(np.float32)
+    gamma, lam = 0.8108071290665859, 0.9452281119742252
+    ad, vd = torch.as_tensor(acts, device=eng.device), torch.as_tensor(vals, device=eng.device)
+    adv, ret = torch.empty((E, n), device=eng.device), torch.empty((E, n), device=eng.device)
+    st = torch.zeros(3, dtype=torch.float64, device=eng.device)
+    for t0 in range(0, T, E):
+        st.zero_()
+        buf.rollout(t0, ad[t0:t0 + E].contiguous(), gae=dict(values=vd[t0:t0 + E].contiguous(), last_values=vd[t0 + E],
+                                                            gamma=gamma, gae_lambda=lam, out=(adv, ret), stats=st))
+        torch.cuda.synchronize()
+        rows, mids = buf.rows.cpu().numpy(), buf.mids.cpu().numpy()
+        starts, rew = buf.starts.cpu().numpy().astype(bool), buf.rewards.cpu().numpy()
+        dn = np.zeros((E, n), bool)
+        for t in range(t0, t0 + E):
+            o = ov.step(acts[t])
+            done = dn[t - t0] = (o["terminated"] | o["truncated"]).astype(bool)
+            r = rows[H + 1 + t]
+            img = r[:, 1:].reshape(n, 3, 7, 7).transpose(0, 2, 3, 1)
+            assert np.array_equal(starts[H + 1 + t], done), t
+            assert np.array_equal(img, np.where(done[:, None, None, None], o["r_image"], o["image"])), t
+            assert np.array_equal(r[:, 0], np.where(done, o["r_dir"], o["dir"])), t
+            assert np.array_equal(tok[mids[H + 1 + t]], np.where(done[:, None], o["r_mission"], o["mission"])), t
+            assert np.array_equal(rew[t], o["reward"].astype(np.float32)), t
+        es = np.zeros((E, n), np.float32)
+        es[1:] = dn[:-1]
+        want_a, want_r = O.gae(rew[t0:t0 + E], vals[t0:t0 + E], es, vals[t0 + E], dn[-1], gamma, lam)
+        assert np.array_equal(adv.cpu().numpy(), want_a), t0
+        assert np.array_equal(ret.cpu().numpy(), want_r), t0
+        sv = st.cpu().numpy()
+        w = want_a.astype(np.float64)
+        assert sv[2] == E * n and abs(sv[0] - w.sum()) <= 1e-9 * np.abs(w).sum() + 1e-9, (t0, sv)
+        assert abs(sv[1] - (w * w).sum()) <= 1e-9 * (w * w).sum(), (t0, sv)
+    a, b = eng.dump_state(), ov.dump()
+    for k in ("grid", "agent", "carrying", "step_count", "mission_done", "mtwords", "pcg", "target"):
+        assert np.array_equal(a[k], b[k]), k
+    assert np.array_equal(a["stored_reward"], b["stored_reward"], equal_nan=True)
     eng.poll_error()
 
 
