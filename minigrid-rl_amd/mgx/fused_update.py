@@ -75,35 +75,76 @@ class ParamArena:
         dev = tensors[0].device
         self.param, self.grad, self.exp_avg, self.exp_avg_sq = (
             torch.zeros(self.words, dtype=torch.float32, device=dev) for _ in range(4))
-        state = getattr(policy, "optimizer", None)
-        state = state.state if state is not None else {}
         self.step = 0
+        for p, (_, o, shape) in zip(tensors, self.layout):
+            if tuple(p.shape) != tuple(shape):
+                raise ValueError("ParamArena: %s is not %s" % (tuple(p.shape), tuple(shape)))
+        self._foreign_state()                                    # ValueError before a parameter is moved
         with torch.no_grad():
             for p, (_, o, shape) in zip(tensors, self.layout):
-                if tuple(p.shape) != tuple(shape):
-                    raise ValueError("ParamArena: %s is not %s" % (tuple(p.shape), tuple(shape)))
                 self._view(self.param, o, shape).copy_(p.data)
                 if p.grad is not None:
                     self._view(self.grad, o, shape).copy_(p.grad)
-                st = state.get(p)
-                if st:
-                    self._view(self.exp_avg, o, shape).copy_(st["exp_avg"])
-                    self._view(self.exp_avg_sq, o, shape).copy_(st["exp_avg_sq"])
-                    self.step = max(self.step, int(st["step"]))
                 p.data = self._view(self.param, o, shape)
                 p.grad = self._view(self.grad, o, shape)
+        self.import_state()
 
     @staticmethod
     def _view(flat, o, shape):
         return flat[o:o + int(torch.Size(shape).numel())].view(shape)
+
+    def _foreign_state(self):
+        """(the optimizer's state entry of each of the 25 tensors or None, whether any of them holds a moment that
+        is not the arena's own view).  ValueError for a foreign moment of the wrong shape or dtype.  Host only: 25
+        pointer comparisons."""
+        opt = getattr(self.policy, "optimizer", None)
+        state = opt.state if opt is not None else {}
+        entries = [state.get(p) or None for p in self.tensors]
+        foreign = False
+        for st, (name, o, shape) in zip(entries, self.layout):
+            for key, flat in (("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq)):
+                t = st.get(key) if st else None
+                if t is None or (t.data_ptr() == flat.data_ptr() + 4 * o and tuple(t.shape) == tuple(shape)
+                                 and t.dtype == flat.dtype):
+                    continue
+                if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32:
+                    raise ValueError("ParamArena: the optimizer's %s of %s is %s %s, not %s %s"
+                                     % (key, name, t.dtype, tuple(t.shape), torch.float32, tuple(shape)))
+                foreign = True
+        return entries, foreign
+
+    def import_state(self):
+        """Take policy.optimizer's state over; returns whether it was foreign.  The arena owns the moments: the
+        optimizer's state is either empty (the arena stays as it is), made of the arena's own views (export_state;
+        the moments stay, the step count is the state's, which torch's Adam may have advanced) or foreign -- some
+        exp_avg / exp_avg_sq is another tensor, as after optimizer.load_state_dict, which replaces the state's
+        tensors where nn.Module.load_state_dict copies in place.  A foreign state is copied in whole: the moments of
+        every tensor that has an entry, zeros for the others, the largest step count; export_state() then makes the
+        optimizer's state views again.  No device work unless the state is foreign."""
+        entries, foreign = self._foreign_state()
+        steps = [int(st["step"]) for st in entries if st and "step" in st]
+        if steps:
+            self.step = max(steps)
+        if not foreign:
+            return False
+        with torch.no_grad():
+            for st, m, v in zip(entries, self.views(self.exp_avg), self.views(self.exp_avg_sq)):
+                for key, view in (("exp_avg", m), ("exp_avg_sq", v)):
+                    if st and st.get(key) is not None:
+                        view.copy_(st[key])
+                    else:
+                        view.zero_()
+        self.export_state()
+        return True
 
     def views(self, flat, which=slice(None)):
         """The tensors of `flat` (one of the four buffers) in layout order."""
         return [self._view(flat, o, shape) for _, o, shape in self.layout[which]]
 
     def attached(self):
-        """Whether every parameter and gradient is still the arena's view (load_state_dict keeps them; an
-        optimizer.zero_grad(set_to_none=True) or p.data = ... elsewhere does not)."""
+        """Whether every parameter and gradient is still the arena's view (the policy's load_state_dict keeps them;
+        an optimizer.zero_grad(set_to_none=True) or p.data = ... elsewhere does not).  Parameters and gradients
+        only: the optimizer's load_state_dict replaces the moments' tensors, which import_state() takes back."""
         for p, (_, o, _) in zip(self.tensors, self.layout):
             if p.data_ptr() != self.param.data_ptr() + 4 * o or p.grad is None or \
                     p.grad.data_ptr() != self.grad.data_ptr() + 4 * o:
@@ -260,9 +301,10 @@ class FusedUpdate:
         self.table.zero_()
         if not self.arena.attached():
             self.arena.attach_grads()  # a torch step in between (optimizer.zero_grad) set them to None
-        st = self.policy.optimizer.state.get(self.arena.tensors[0])
-        if st and "step" in st:        # torch's Adam stepped on the exported state (its moments are the arena's views)
-            self.arena.step = int(st["step"])
+        # torch's Adam stepped on the exported state (views: only the step count moves), or a checkpoint was loaded
+        # into the live optimizer (foreign tensors: moments and step are copied in).  graph_begin reads arena.step
+        # for the schedule's first step, so it runs after this.
+        self.arena.import_state()
         if not self.arena.attached():
             raise RuntimeError("FusedUpdate: the policy's parameters are no longer views of the arena")
 

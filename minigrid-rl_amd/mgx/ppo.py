@@ -548,6 +548,8 @@ class Trainer:
             from .fused_update import FusedUpdate
             self.update = FusedUpdate(self.policy, eng)
         up = self.update
+        # prepare imports an optimizer state loaded since the last call (ParamArena.import_state); graph_begin below
+        # starts the Adam schedule at arena.step + 1, so it must come after
         up.prepare(buf.buf)
         T, N, bs = buf.T, buf.N, cfg.batch_size
         rollout = (buf.actions, buf.values, buf.log_probs, buf.advantages, buf.returns)

@@ -263,10 +263,15 @@ def _adam_inputs(n, target_norm):
     return param, grads
 
 
-def _torch_adam(param, grads, max_norm, dtype, device):
-    """clip_grad_norm_ + torch.optim.Adam, three steps -> per step (param, exp_avg, exp_avg_sq, grad, total norm)."""
+def _torch_adam(param, grads, max_norm, dtype, device, state=None):
+    """clip_grad_norm_ + torch.optim.Adam, three steps -> per step (param, exp_avg, exp_avg_sq, grad, total norm).
+    state: (exp_avg, exp_avg_sq, first step) the optimizer starts from, as after load_state_dict."""
     p = torch.nn.Parameter(param.to(device=device, dtype=dtype).clone())
     opt = torch.optim.Adam([p], lr=LR, betas=BETAS, eps=ADAM_EPS)
+    if state is not None:
+        opt.state[p] = {"step": torch.tensor(float(state[2] - 1)),
+                        "exp_avg": state[0].to(device=device, dtype=dtype).clone(),
+                        "exp_avg_sq": state[1].to(device=device, dtype=dtype).clone()}
     out = []
     for g in grads:
         p.grad = g.to(device=device, dtype=dtype).clone()
@@ -281,32 +286,46 @@ def _torch_adam(param, grads, max_norm, dtype, device):
     return out
 
 
-def _kernel_adam(param, grads, max_norm, grad_scale=1.0):
+def _kernel_adam(param, grads, max_norm, grad_scale=1.0, state=None):
     from mgx.fused_update import adam_step
     n = param.numel()
     p = param.cuda().clone()
-    m, v = torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")
+    m, v, first = torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda"), 1
+    if state is not None:
+        m, v, first = state[0].cuda().clone(), state[1].cuda().clone(), state[2]
     norm = torch.zeros(1, device="cuda")
     out = []
     for i, g in enumerate(grads):
         gg = g.cuda().clone()
-        adam_step(p, gg, m, v, LR, i + 1, betas=BETAS, eps=ADAM_EPS, max_grad_norm=max_norm, grad_scale=grad_scale,
-                  total_norm=norm)
+        adam_step(p, gg, m, v, LR, first + i, betas=BETAS, eps=ADAM_EPS, max_grad_norm=max_norm,
+                  grad_scale=grad_scale, total_norm=norm)
         torch.cuda.synchronize()
         out.append((p.clone(), m.clone(), v.clone(), gg, norm.clone()))
     return out
 
 
+RESUMED_STEP = 12345                               # a resumed run: Adam's bias corrections are all but 1
+
+
+def _adam_state(n):
+    """(exp_avg, exp_avg_sq >= 0, first step) of a run resumed at RESUMED_STEP: random moments of the size the
+    clipped gradients of _adam_inputs leave behind."""
+    g = torch.Generator().manual_seed(4000 + n)
+    scale = MAX_NORM / math.sqrt(n)
+    return scale * torch.randn(n, generator=g), (scale * torch.randn(n, generator=g)) ** 2, RESUMED_STEP
+
+
 def _adam_compare(n, case):
     """Three consecutive mgx_adam_step calls against the yardstick -> ([(name, dev, e_torch, bound)], the kernel's
     outputs, the inputs).  clip: gradient norm 4 x max_grad_norm; noclip: a quarter of it; off: max_grad_norm = 0
-    with the large gradients."""
+    with the large gradients; resumed: clip, from _adam_state's moments and step in every path."""
     target = MAX_NORM * (0.25 if case == "noclip" else 4.0)
     max_norm = 0.0 if case == "off" else MAX_NORM
+    state = _adam_state(n) if case == "resumed" else None
     param, grads = _adam_inputs(n, target)
-    ref = _torch_adam(param, grads, max_norm, torch.float64, "cpu")
-    t32 = _torch_adam(param, grads, max_norm, torch.float32, "cuda")
-    got = _kernel_adam(param, grads, max_norm)
+    ref = _torch_adam(param, grads, max_norm, torch.float64, "cpu", state)
+    t32 = _torch_adam(param, grads, max_norm, torch.float32, "cuda", state)
+    got = _kernel_adam(param, grads, max_norm, state=state)
     rows = []
     for step in range(3):
         for j, name in enumerate(("param", "exp_avg", "exp_avg_sq", "grad")):
@@ -314,7 +333,7 @@ def _adam_compare(n, case):
             bound = max(4.0 * e_torch, 4.0 * EPS32 * float(ref[step][j].abs().max()))
             dev = float((got[step][j].double().cpu() - ref[step][j]).abs().max())
             print("n %d %s step %d %s: kernel max |dev| %.3e, torch fp32 %.3e, bound %.3e, ratio %.2f"
-                  % (n, case, step + 1, name, dev, e_torch, bound, dev / bound))
+                  % (n, case, step + 1 if state is None else state[2] + step, name, dev, e_torch, bound, dev / bound))
             rows.append(("step %d %s" % (step + 1, name), dev, e_torch, bound))
         e_torch = abs(t32[step][4] - ref[step][4])
         bound = max(4.0 * e_torch, 4.0 * EPS32 * abs(ref[step][4]))
@@ -323,8 +342,8 @@ def _adam_compare(n, case):
               % (n, case, step + 1, ref[step][4], dev, e_torch, bound))
         rows.append(("step %d total_norm" % (step + 1), dev, e_torch, bound))
         clipped = float(ref[step][3].norm()) < 0.99 * target
-        assert clipped == (case == "clip")
-    return rows, got, (param, grads, max_norm)
+        assert clipped == (case in ("clip", "resumed"))
+    return rows, got, (param, grads, max_norm, 1.0, state)
 
 
 @pytest.mark.parametrize("case", ["clip", "noclip", "off"])
@@ -339,6 +358,39 @@ def test_adam_step_parity(size, case):
     for a, b in zip(got, again):
         for x, y in zip(a, b):
             assert torch.equal(x, y)
+    bad = [r for r in rows if not r[1] <= r[3]]
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("size", [0, 5])
+def test_adam_step_parity_resumed(size):
+    """What a resumed run asks of mgx_adam_step: three steps from imported non-zero moments (exp_avg_sq >= 0) at
+    step 12,345, against fp64 clip_grad_norm_ + torch.optim.Adam whose state was set to the same moments and step,
+    by the file's yardstick.  The same steps through adam_schedule(first_step=12345) + mgx_adam_step_sched equal the
+    by-value calls bit for bit."""
+    _gpu()
+    from mgx.fused_update import adam_schedule, adam_step_sched
+    n = _adam_sizes()[size]
+    rows, got, inputs = _adam_compare(n, "resumed")
+    param, grads, max_norm, _, state = inputs
+    assert state[2] == RESUMED_STEP and state[0].any() and bool((state[1] >= 0).all()) and state[1].any()
+    again = _kernel_adam(*inputs)
+    for a, b in zip(got, again):
+        for x, y in zip(a, b):
+            assert torch.equal(x, y)
+    table = adam_schedule([LR] * 3, first_step=RESUMED_STEP, betas=BETAS, eps=ADAM_EPS).cuda()
+    cursor = torch.zeros(2, dtype=torch.int32, device="cuda")
+    p, m, v = param.cuda().clone(), state[0].cuda().clone(), state[1].cuda().clone()
+    norm = torch.zeros(1, device="cuda")
+    for i, g in enumerate(grads):
+        gg = g.cuda().clone()
+        adam_step_sched(p, gg, m, v, table, cursor, betas=BETAS, eps=ADAM_EPS, max_grad_norm=max_norm,
+                        total_norm=norm)
+        torch.cuda.synchronize()
+        for name, x, y in zip(("param", "exp_avg", "exp_avg_sq", "grad", "total_norm"), (p, m, v, gg, norm), got[i]):
+            assert x.shape == y.shape and torch.equal(x.view(torch.int32), y.view(torch.int32)), (i, name)
+        assert cursor.tolist() == [i + 1, 0]
+    assert not torch.equal(got[2][0], param.cuda()) and not torch.equal(got[2][1], state[0].cuda())
     bad = [r for r in rows if not r[1] <= r[3]]
     assert not bad, bad
 
