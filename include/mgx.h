@@ -655,6 +655,44 @@ typedef struct mgx_eval_record_args {
 mgx_status mgx_eval_record(int64_t n_envs, int64_t n_eval_episodes, int64_t cap, int64_t step_offset,
                            const mgx_eval_record_args *a, void *stream);
 
+/* ---- The shortest-path expert on the device (added within ABI 9) ----------------------------------------
+ * A stateless expert for demonstrations (behaviour cloning, DAgger) and as an optimal-length yardstick: the action
+ * and the remaining cost of every env, from the env's current state alone (EnvState and the grid).  The reference's
+ * counterpart is src/experts.py (a per-env Python A* over a full-grid observation, no locked doors), cloned by
+ * `algo: bc` (src/hydra_configs/imitation.yaml).  mgx/expert.py expert_reference is the normative definition; this
+ * call returns the same integers for the same state.
+ *
+ * Cost model over states (x, y, dir): LEFT / RIGHT cost 1; FORWARD into an empty cell or an open door costs 1;
+ * entering a closed door costs 2 (TOGGLE, then FORWARD); entering a locked door costs 2, but only while carrying
+ * the key of its colour; everything else is impassable (lava, walls, objects, any goal that is not the final
+ * cell).  The agent's own cell is always a valid start.  D(s) is the cost-to-go to a goal set G.  The first action
+ * is the argmin over [the forward move, LEFT, RIGHT] of edge cost + D(successor), ties in that order; the forward
+ * move is TOGGLE when the front cell is a door that must be opened first.
+ *
+ * Rules, the first that applies decides (action, cost):
+ *   1. mission_done: DONE, 0.
+ *   2. no target cell (tx == 255): the target action if there is one, cost 1 ('drop' completes on the action
+ *      alone); else ('move' missions) DONE, -1: unsupported.
+ *   3. needed = the hand holds a key whose colour some locked door of the grid has.  Target action PICKUP with a
+ *      full hand that is not needed: the drop routine, -2.
+ *   4. route to the mission.  At-cell missions (target action 255 or 0): G = the target cell in any direction,
+ *      which may be entered as the final move; cost D (standing on it already: DONE, 0).  Facing missions: G =
+ *      every neighbour of the target, facing it; cost D + 1; at D == 0 the action is the target action, or (PICKUP
+ *      with a full hand) the drop routine, -2.
+ *   5. unreachable with a full hand that is not needed: the drop routine, -2.
+ *   6. unreachable with an empty hand: G = every state facing a key, or a key-holding box, whose colour some
+ *      locked door has; the route's first action, at D == 0 PICKUP for a key and TOGGLE for a box; cost -3.
+ *   7. otherwise DONE, -4: give up.
+ * Drop routine: the first empty cell among front, right, left, behind decides: DROP, RIGHT, LEFT, RIGHT; none: DONE.
+ *
+ * actions_dev: [N] int32 (action_bytes = 4) or int64 (8); cost_dev: optional i32 [N].  Reads the handle's state and
+ * grids and nothing else of it, writes only its outputs; one launch (one lane per env, one wave per 64 envs, a
+ * layered search bounded by 8 size^2 layers).  Only enqueues on `stream` (no allocation, no host sync): it can sit
+ * in a captured graph between two mgx_step_compact calls.  MGX_ERR_INVALID before any HIP call for: a null handle
+ * or actions_dev, action_bytes other than 4 or 8. */
+mgx_status mgx_expert_act(mgx_handle *h, void *actions_dev, int action_bytes, int32_t *cost_dev /* optional */,
+                          void *stream);
+
 /* Makes `stream` wait for the in-flight refill, if any (no host sync). */
 mgx_status mgx_join(mgx_handle *h, void *stream);
 

@@ -2740,6 +2740,7 @@ __global__ __launch_bounds__(256) void mgx_gather_kernel(const uint8_t *__restri
 #include "mgx_mission.h"   // mgx_mission_forward / mgx_mission_backward: the mission Embedding + GRU
 #include "mgx_update.h"    // mgx_ppo_loss / mgx_adam_step: the PPO loss and the clip + Adam step
 #include "mgx_eval.h"      // mgx_eval_record: evaluate_policy's per-step episode accounting
+#include "mgx_expert.h"    // mgx_expert_act: the shortest-path expert over the engine's own state
 
 // ================================================================== host side
 thread_local std::string g_last_error;
@@ -4292,6 +4293,21 @@ mgx_status mgx_eval_record(int64_t n_envs, int64_t n_eval_episodes, int64_t cap,
     a.n = n_envs; a.n_eval = n_eval_episodes; a.cap = cap; a.step_offset = step_offset;
     const int64_t groups = (n_envs + EVAL_THREADS - 1) / EVAL_THREADS;
     hipLaunchKernelGGL(mgx_eval_record_kernel, dim3((unsigned)groups), dim3(EVAL_THREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return MGX_OK;
+}
+
+// ---- the shortest-path expert (mgx_expert.h): reads the handle's state and grids, writes only its outputs
+mgx_status mgx_expert_act(mgx_handle *h, void *actions_dev, int action_bytes, int32_t *cost_dev, void *stream) {
+    if (!h || !actions_dev) return fail(MGX_ERR_INVALID, "mgx_expert_act: null argument");
+    if (action_bytes != 4 && action_bytes != 8) return fail(MGX_ERR_INVALID, "mgx_expert_act: action_bytes must be 4 or 8");
+    if (h->kp.S < 5 || h->kp.S > 16 || h->kp.GS > 16 * (EX_GRID_SLOTS - 1) || (h->kp.GS & 15))
+        return fail(MGX_ERR_INVALID, "mgx_expert_act: grid size outside 5..16");
+    ExpertArgs a;
+    a.state = h->kp.state; a.grid = h->kp.grid; a.actions = actions_dev; a.cost = cost_dev;
+    a.n = h->kp.n; a.S = h->kp.S; a.GS = h->kp.GS; a.action_bytes = action_bytes;
+    const int64_t groups = (a.n + EX_THREADS - 1) / EX_THREADS;
+    hipLaunchKernelGGL(mgx_expert_kernel, dim3((unsigned)groups), dim3(EX_THREADS), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return MGX_OK;
 }

@@ -8,7 +8,9 @@ from .describe import LLMDescriptionWrapper  # noqa: F401
 from .engine import MgxEngine, gae, gae_dones, random_actions  # noqa: F401
 from .evaluation import (EvalCallback, GraphEvaluator, StopTrainingOnRewardThreshold, evaluate_policy,  # noqa: F401
                          evaluate_test_protocol, summarize_missions)
+from .expert import ExpertActor, expert_reference  # noqa: F401
+from .imitation import BCTrainer, Demonstrations, bc_loss, collect_demonstrations  # noqa: F401
 from .moe import FusedMoEActor, MoEPolicy, route_by_task, route_from_gate  # noqa: F401
 from .vec_env import MgxVecEnv  # noqa: F401
 
-__all__ = ["EvalCallback", "FusedMoEActor", "GraphEvaluator", "LLMDescriptionWrapper", "MgxEngine", "MgxError", "MgxVecEnv", "MoEPolicy", "StopTrainingOnRewardThreshold", "evaluate_policy", "evaluate_test_protocol", "gae", "gae_dones", "mission_text", "random_actions", "route_by_task", "route_from_gate", "summarize_missions"]
+__all__ = ["BCTrainer", "Demonstrations", "EvalCallback", "ExpertActor", "FusedMoEActor", "GraphEvaluator", "LLMDescriptionWrapper", "MgxEngine", "MgxError", "MgxVecEnv", "MoEPolicy", "StopTrainingOnRewardThreshold", "bc_loss", "collect_demonstrations", "evaluate_policy", "evaluate_test_protocol", "expert_reference", "gae", "gae_dones", "mission_text", "random_actions", "route_by_task", "route_from_gate", "summarize_missions"]

@@ -32,7 +32,7 @@ EXPORTS = ("mgx_last_error", "mgx_abi_version", "mgx_create", "mgx_destroy", "mg
            "mgx_mission_workspace_words", "mgx_mission_forward", "mgx_mission_backward",
            "mgx_ppo_loss_scratch_words", "mgx_ppo_loss", "mgx_adam_scratch_words", "mgx_adam_step",
            "mgx_mission_forward_rows", "mgx_mission_backward_rows", "mgx_adam_schedule", "mgx_adam_step_sched",
-           "mgx_eval_record", "mgx_policy_moe_scratch_words", "mgx_policy_act_moe")
+           "mgx_eval_record", "mgx_policy_moe_scratch_words", "mgx_policy_act_moe", "mgx_expert_act")
 CLOCK_CLASSES = 4   # == MGX_CLOCK_CLASSES (include/mgx.h)
 MOE_MAX_EXPERTS = 8     # == MGX_MOE_MAX_EXPERTS (include/mgx.h)
 MOE_RECORD_WORDS = 32   # == MGX_MOE_RECORD_WORDS (include/mgx.h)
@@ -244,6 +244,7 @@ def load():
                                     ctypes.POINTER(MgxAdamSched)]
     L.mgx_adam_step_sched.argtypes = [P, P, P, P, I64, ctypes.POINTER(MgxAdamArgs), P, ctypes.c_int32, P, P, P, I64, P]
     L.mgx_eval_record.argtypes = [I64, I64, I64, I64, ctypes.POINTER(MgxEvalRecordArgs), P]
+    L.mgx_expert_act.argtypes = [P, P, I, P, P]
     L.mgx_set_clock.argtypes = [P, P, I, ctypes.POINTER(I)]
     L.mgx_clock_words.argtypes = [P, I]
     L.mgx_clock_words.restype = I64
