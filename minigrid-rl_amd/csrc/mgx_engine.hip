@@ -3750,7 +3750,7 @@ mgx_status mgx_observe_compact(mgx_handle *h, uint8_t *row_dev, uint8_t *mission
     return MGX_OK;
 }
 
-// The sample addressing shared by mgx_gather_ring, mgx_policy_act and mgx_policy_backward, checked and filled into *s.
+// The sample addressing shared by mgx_gather_ring and the mgx_policy_* entry points, checked and filled into *s.
 // 0: fine; 1: a null pointer or a count out of range; 2: a ring that cannot hold n_stack rows.  The callers word
 // their own messages.
 static int sample_addr(const mgx_handle *h, const uint8_t *rows_dev, const uint8_t *mission_ids_dev,
@@ -3847,6 +3847,28 @@ int64_t mgx_policy_blob_words(int n_stack) {
     return n_stack >= 1 && n_stack <= MAX_NSTACK ? (int64_t)pol_blob(n_stack).words : -1;
 }
 
+// What is wrong with sample_addr's result, for the message after the entry point's name; nullptr: nothing
+static const char *sample_addr_bad(int bad) {
+    return bad == 1 ? "bad sample addressing" : bad == 2 ? "the ring must hold n_stack rows" : nullptr;
+}
+
+// mgx_policy_act and mgx_policy_act_moe: the checks of mode, counter and outputs, which fill *o; returns as above
+static const char *pol_out(int mode, const void *counter_dev, const mgx_act_out *out, PolOut *o) {
+    if (mode < 0 || mode > 2) return "mode must be 0, 1 or 2";
+    if (mode == 2 && !counter_dev) return "mode 2 needs counter_dev";
+    if (mode != 0 && (!out->actions_dev || !out->log_probs_dev)) return "modes 1 and 2 need actions_dev and log_probs_dev";
+    *o = PolOut{(long long *)out->actions_dev, out->values_dev, out->log_probs_dev, out->logits_dev};
+    return nullptr;
+}
+
+// Launches kernel<n_stack>(args) over `groups` workgroups with mgx_policy_kernel's block and dynamic LDS; false, and
+// nothing launched, for an n_stack outside 1 .. MAX_NSTACK
+#define POL_LAUNCH(kernel, n_stack, groups, stream, args)                                                     \
+    for_n_stack(n_stack, [&](auto kk) {                                                                        \
+        constexpr int KK = decltype(kk)::value;                                                                \
+        hipLaunchKernelGGL(kernel<KK>, dim3(groups), dim3(POL_THREADS), pol_lds_bytes(KK), (hipStream_t)stream, args); \
+    })
+
 mgx_status mgx_policy_act(const mgx_handle *h, const uint8_t *rows_dev, const uint8_t *mission_ids_dev,
                           const uint8_t *starts_dev, int64_t n_envs, int64_t ring_rows, const int64_t *index_dev,
                           int64_t n_samples, const uint8_t *terminal_rows_dev, const mgx_policy *pol,
@@ -3854,26 +3876,16 @@ mgx_status mgx_policy_act(const mgx_handle *h, const uint8_t *rows_dev, const ui
     if (!pol || !out) return fail(MGX_ERR_INVALID, "mgx_policy_act: null policy / outputs");
     if (!pol->blob_dev || !pol->mission_feat_dev) return fail(MGX_ERR_INVALID, "mgx_policy_act: null blob / mission features");
     if (n_samples <= 0) return fail(MGX_ERR_INVALID, "mgx_policy_act: n_samples must be > 0");
-    if (pol->mode < 0 || pol->mode > 2) return fail(MGX_ERR_INVALID, "mgx_policy_act: mode must be 0, 1 or 2");
-    if (pol->mode == 2 && !pol->counter_dev) return fail(MGX_ERR_INVALID, "mgx_policy_act: mode 2 needs counter_dev");
-    if (pol->mode != 0 && (!out->actions_dev || !out->log_probs_dev))
-        return fail(MGX_ERR_INVALID, "mgx_policy_act: modes 1 and 2 need actions_dev and log_probs_dev");
     PolArgs a;
-    const int bad = sample_addr(h, rows_dev, mission_ids_dev, starts_dev, n_envs, ring_rows, index_dev, n_samples, &a.s);
-    if (bad == 1) return fail(MGX_ERR_INVALID, "mgx_policy_act: bad sample addressing");
-    if (bad == 2) return fail(MGX_ERR_INVALID, "mgx_policy_act: the ring must hold n_stack rows");
+    const char *bad = pol_out(pol->mode, pol->counter_dev, out, &a.out);
+    if (!bad) bad = sample_addr_bad(sample_addr(h, rows_dev, mission_ids_dev, starts_dev, n_envs, ring_rows, index_dev, n_samples, &a.s));
+    if (bad) return fail(MGX_ERR_INVALID, std::string("mgx_policy_act: ") + bad);
     a.newest = terminal_rows_dev;
     a.blob = pol->blob_dev; a.mfeat = pol->mission_feat_dev; a.mode = pol->mode; a.seed = pol->seed;
     a.ctr = (unsigned long long *)pol->counter_dev;
-    a.actions = (long long *)out->actions_dev; a.values = out->values_dev; a.log_probs = out->log_probs_dev;
-    a.logits = out->logits_dev;
-    const int64_t nblk = (n_samples + POL_TILE - 1) / POL_TILE;
-    const bool launched = for_n_stack(h->kp.n_stack, [&](auto kk) {
-        constexpr int KK = decltype(kk)::value;
-        hipLaunchKernelGGL(mgx_policy_kernel<KK>, dim3((unsigned)nblk), dim3(POL_THREADS), pol_lds_bytes(KK),
-                           (hipStream_t)stream, a);
-    });
-    if (!launched) return fail(MGX_ERR_INVALID, "mgx_policy_act: n_stack out of range");
+    const unsigned groups = (unsigned)((n_samples + POL_TILE - 1) / POL_TILE);
+    if (!POL_LAUNCH(mgx_policy_kernel, h->kp.n_stack, groups, stream, a))
+        return fail(MGX_ERR_INVALID, "mgx_policy_act: n_stack out of range");
     HIP_TRY(hipGetLastError());
     return MGX_OK;
 }
@@ -3885,17 +3897,14 @@ mgx_status mgx_policy_bootstrap(const mgx_handle *h, const uint8_t *rows_dev, co
     if (!pol || !b) return fail(MGX_ERR_INVALID, "mgx_policy_bootstrap: null policy / bootstrap arguments");
     if (!pol->blob_dev || !pol->mission_feat_dev)
         return fail(MGX_ERR_INVALID, "mgx_policy_bootstrap: null blob / mission features");
-    if (!h || !rows_dev || !mission_ids_dev || !starts_dev || !terminal_rows_dev || !b->truncated_dev ||
-        !b->terminated_dev || !b->rewards_dev || !b->list_dev || !b->count_dev)
+    if (!terminal_rows_dev || !b->truncated_dev || !b->terminated_dev || !b->rewards_dev || !b->count_dev)
         return fail(MGX_ERR_INVALID, "mgx_policy_bootstrap: null argument");
-    if (n_envs <= 0) return fail(MGX_ERR_INVALID, "mgx_policy_bootstrap: n_envs must be > 0");
-    if (ring_rows < 0 || row < 0 || (ring_rows > 0 && row >= ring_rows))
+    if (row < 0 || (ring_rows > 0 && row >= ring_rows))               // (before sample_addr, which reads the handle)
         return fail(MGX_ERR_INVALID, "mgx_policy_bootstrap: row outside the buffer");
-    if (ring_rows > 0 && ring_rows < h->kp.n_stack)
-        return fail(MGX_ERR_INVALID, "mgx_policy_bootstrap: the ring must hold n_stack rows");
-    PolBootArgs a;
-    a.rows = rows_dev; a.mids = mission_ids_dev; a.starts = starts_dev;
-    a.N = n_envs; a.R = ring_rows; a.row = row;
+    PolBootArgs a;                                                    // the samples: the list, n_envs entries at most
+    const char *bad = sample_addr_bad(sample_addr(h, rows_dev, mission_ids_dev, starts_dev, n_envs, ring_rows, b->list_dev, n_envs, &a.s));
+    if (bad) return fail(MGX_ERR_INVALID, std::string("mgx_policy_bootstrap: ") + bad);
+    a.row = row;
     a.newest = terminal_rows_dev;
     a.blob = pol->blob_dev; a.mfeat = pol->mission_feat_dev;
     a.truncated = b->truncated_dev; a.terminated = b->terminated_dev;
@@ -3906,11 +3915,7 @@ mgx_status mgx_policy_bootstrap(const mgx_handle *h, const uint8_t *rows_dev, co
     hipLaunchKernelGGL(mgx_boot_list_kernel, dim3(1), dim3(BOOT_THREADS), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     const unsigned groups = (unsigned)((n_envs + POL_TILE - 1) / POL_TILE);   // the count is known on the device only
-    for_n_stack(K, [&](auto kk) {
-        constexpr int KK = decltype(kk)::value;
-        hipLaunchKernelGGL(mgx_policy_boot_kernel<KK>, dim3(groups), dim3(POL_THREADS), pol_lds_bytes(KK),
-                           (hipStream_t)stream, a);
-    });
+    POL_LAUNCH(mgx_policy_boot_kernel, K, groups, stream, a);
     HIP_TRY(hipGetLastError());
     return MGX_OK;
 }
@@ -3934,18 +3939,15 @@ mgx_status mgx_policy_act_moe(const mgx_handle *h, const uint8_t *rows_dev, cons
     if (!pol->route_dev || !pol->scratch_dev) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: null route / scratch");
     if ((uintptr_t)pol->scratch_dev & 7) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: scratch_dev must be 8-byte aligned");
     if (n_samples <= 0) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: n_samples must be > 0");
-    if (pol->mode < 0 || pol->mode > 2) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: mode must be 0, 1 or 2");
-    if (pol->mode == 2 && !pol->counter_dev) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: mode 2 needs counter_dev");
-    if (pol->mode != 0 && (!out->actions_dev || !out->log_probs_dev))
-        return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: modes 1 and 2 need actions_dev and log_probs_dev");
+    PolMoeArgs a;
+    const char *bad = pol_out(pol->mode, pol->counter_dev, out, &a.out);
+    if (bad) return fail(MGX_ERR_INVALID, std::string("mgx_policy_act_moe: ") + bad);
     const int64_t words = mgx_policy_moe_scratch_words(n_samples, pol->n_experts);
     if (words < 0) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: n_samples out of range");
     if (pol->scratch_words < words)
         return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: scratch_words below mgx_policy_moe_scratch_words");
-    PolMoeArgs a;
-    const int bad = sample_addr(h, rows_dev, mission_ids_dev, starts_dev, n_envs, ring_rows, index_dev, n_samples, &a.s);
-    if (bad == 1) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: bad sample addressing");
-    if (bad == 2) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: the ring must hold n_stack rows");
+    bad = sample_addr_bad(sample_addr(h, rows_dev, mission_ids_dev, starts_dev, n_envs, ring_rows, index_dev, n_samples, &a.s));
+    if (bad) return fail(MGX_ERR_INVALID, std::string("mgx_policy_act_moe: ") + bad);
     const int K = h->kp.n_stack;
     if (K < 1 || K > MAX_NSTACK) return fail(MGX_ERR_INVALID, "mgx_policy_act_moe: n_stack out of range");
     const int64_t cap = n_samples + (POL_TILE - 1) * pol->n_experts;   // the most entries a list can hold
@@ -3959,16 +3961,10 @@ mgx_status mgx_policy_act_moe(const mgx_handle *h, const uint8_t *rows_dev, cons
     a.rec = pol->scratch_dev;
     a.list = reinterpret_cast<int64_t *>(pol->scratch_dev + MOE_REC);
     a.pos = pol->scratch_dev + MOE_REC + 2 * cap;
-    a.actions = (long long *)out->actions_dev; a.values = out->values_dev; a.log_probs = out->log_probs_dev;
-    a.logits = out->logits_dev;
     hipLaunchKernelGGL(mgx_moe_route_kernel, dim3(1), dim3(MOE_THREADS), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     const unsigned groups = (unsigned)(cap / POL_TILE);               // >= the live tiles (mgx_policy_moe_kernel)
-    for_n_stack(K, [&](auto kk) {
-        constexpr int KK = decltype(kk)::value;
-        hipLaunchKernelGGL(mgx_policy_moe_kernel<KK>, dim3(groups), dim3(POL_THREADS), pol_lds_bytes(KK),
-                           (hipStream_t)stream, a);
-    });
+    POL_LAUNCH(mgx_policy_moe_kernel, K, groups, stream, a);
     HIP_TRY(hipGetLastError());
     return MGX_OK;
 }

@@ -10,13 +10,15 @@
 // feature i of its own sample, consecutive lanes hit consecutive banks.  All 64 lanes are busy in every stage of a
 // full tile; a tail tile computes zeros in its spare lanes and writes nothing for them.
 //
-// Stages A to F are the pol_* function templates below, each taking its source and destination LDS regions: they are
-// the network's one forward pass, run by mgx_policy_kernel here and by pass (a) of mgx_policy_grad_kernel
-// (mgx_policy_grad.h), so the gradient is that of the logits mgx_policy_act returns.
+// Stages A to F are the pol_* function templates below, each taking its source and destination LDS regions; pol_trunk
+// is their sequence, the one place that defines their order, the barrier after each and which region (PolLds) becomes
+// which.  It is the network's one forward pass, run by the three act-side kernels here and by pass (a) of
+// mgx_policy_grad_kernel (mgx_policy_grad.h): bootstrap, mixture and gradient are those of what mgx_policy_act returns.
 //
 //   A   pol_stage_src   per (sample, slot): source row / validity (stack_slot: mgx_gather's walk-back, ring wrap and
 //                       terminal rows included)
-//   A2  pol_stage_rows  rows -> LDS as dwords [slot][37][65] (coalesced along a row; empty slot = zeros)
+//   A2  pol_stage_rows  rows -> LDS as dwords [slot][37][65] (coalesced along a row; empty slot = zeros); then each
+//                       lane's row of the mission-feature table (pol_feat_row) and the caller's after_rows
 //   B   pol_conv1       conv1 2x2 + ReLU + MaxPool 2: rows -> P[144]; before it each lane packs its K direction bytes
 //                       into a register (pol_dsel)
 //   C   pol_conv2       conv2 2x2 + ReLU: P -> C2[128]
@@ -24,9 +26,11 @@
 //   E   pol_l0          policy_net L0 | value_net_body L0 (208 -> 64 each, Tanh): F + mission_feat[mid][v-1][128]
 //                       (global) -> H1[128]
 //   F   pol_l1          policy_net L1 | value_net_body L1 (64 -> 64 each, Tanh): H1 -> H2[128]
-//   G   action_net (7) and value_net (1), arg-max / inverse-cdf sample, log-prob: wave 0 of mgx_policy_kernel
-// mgx_policy_kernel has two LDS regions in all, X = max(37 K, 128) rows (the rows, then C2, then H1) and P = 144 rows
-// (the pooled maps, then F, then H2) of 65 dwords: 79 KB at n_stack 4, two workgroups per CU.
+//   G   pol_heads       action_net (7) and value_net (1), arg-max / inverse-cdf sample, log-prob: wave 0 of
+//                       mgx_policy_kernel and mgx_policy_moe_kernel (mgx_policy_boot_kernel: the value head alone);
+//                       not part of pol_trunk
+// The three act-side kernels have two LDS regions in all (pol_act_lds), X = max(37 K, 128) rows (the rows, then C2,
+// then H1) and P = 144 rows (the pooled maps, then F, then H2) of 65 dwords: 79 KB at n_stack 4, two workgroups per CU.
 // fp32 throughout, every multiply-add an explicit fmaf (the library is built with -ffp-contract=off).
 #ifndef MGX_POLICY_H_
 #define MGX_POLICY_H_
@@ -77,6 +81,12 @@ struct SampleAddr {
     int64_t B;
 };
 
+// The outputs of mgx_policy_act and mgx_policy_act_moe (an mgx_act_out; pol_out in mgx_engine.hip checks and fills it)
+struct PolOut {
+    long long *actions;
+    float *values, *log_probs, *logits;
+};
+
 struct PolArgs {
     SampleAddr s;
     const uint8_t *newest;
@@ -84,8 +94,12 @@ struct PolArgs {
     int mode;
     uint64_t seed;
     unsigned long long *ctr;
-    long long *actions;
-    float *values, *log_probs, *logits;
+    PolOut out;
+};
+
+// The forward pass's LDS regions, [feature][POL_LS] floats; one may lie over another that is dead when it is written
+struct PolLds {
+    float *rows, *P, *C2, *F, *H1, *H2;
 };
 
 // acc[o] += sum_i w[o * ldw + i] * x(i), i ascending, x four at a time through `load4` (each value feeds NO chains)
@@ -143,7 +157,7 @@ __device__ __forceinline__ void pol_conv2x2(const float (&in)[9], const float *_
 
 // ---- The forward pass, stage by stage.  Common arguments: tid = thread of the workgroup, lane = tid & 63 = the
 // sample, wv = the wave (wave-uniform, so that weight addresses stay scalar), W = the weight blob; activations are
-// [feature][POL_LS] floats in LDS.  The caller puts a barrier between two stages.
+// [feature][POL_LS] floats in LDS.  pol_trunk, after them, puts a barrier between two stages.
 
 // ---- A: source row (nullptr: empty slot) and mission id (-1) of every (sample, slot) of the tile of nb samples at b0;
 // slot K-1 is the newest (mgx_gather_kernel's rules)
@@ -334,6 +348,46 @@ __device__ __forceinline__ void pol_l1(const float *__restrict__ W, int wv, int 
     }
 }
 
+// ---- A to F in order, with the barrier after each: the forward pass of the tile of nb samples at b0 of s.index, from
+// compact rows to r.H2; written here and nowhere else.  s_src / s_mid: stage A's [64 K] arrays in LDS; mfeat: the table
+// [256][K][128]; after_rows(feature row): the caller's own work between A2 and its barrier (mgx_policy_grad_kernel
+// stages its cotangents there).  Returns what a lane keeps of its sample once the rows are dead.
+struct PolLane { int v; uint32_t dsel; };  // valid slots; pol_dsel
+template <int K, class AfterRows>
+__device__ __forceinline__ PolLane pol_trunk(const SampleAddr &s, const uint8_t *newest, int64_t b0, int nb, int tid,
+                                             int lane, int wv, const float *__restrict__ W, const float *mfeat,
+                                             const uint8_t **s_src, int *s_mid, const PolLds &r,
+                                             AfterRows after_rows) {
+    PolLane l;
+    pol_stage_src<K>(s, newest, b0, nb, tid, s_src, s_mid);           // A
+    __syncthreads();
+    pol_stage_rows<K>(s_src, tid, r.rows);                            // A2
+    const int frow = pol_feat_row<K>(s_mid, lane, nb, l.v);
+    const float *__restrict__ mf = mfeat + (size_t)frow * 128;
+    after_rows(frow);
+    __syncthreads();
+    const uint8_t *xb = reinterpret_cast<const uint8_t *>(r.rows) + lane * 4;
+    l.dsel = pol_dsel<K>(xb);
+    pol_conv1<K>(W, wv, lane, xb, r.P);                               // B
+    __syncthreads();                                                  // rows dead from here
+    pol_conv2<K>(W, wv, lane, r.P, r.C2);                             // C
+    __syncthreads();
+    pol_conv3_dir<K>(W, wv, lane, l.dsel, l.v, r.C2, r.F);            // D
+    __syncthreads();
+    pol_l0<K>(W, wv, lane, mf, r.F, r.H1);                            // E
+    __syncthreads();
+    pol_l1<K>(W, wv, lane, r.H1, r.H2);                               // F
+    __syncthreads();
+    return l;
+}
+// The act-side kernels' regions, two in all (pol_lds_bytes): X = the rows, then C2, then H1; P = P, then F, then H2
+template <int K>
+__device__ __forceinline__ PolLds pol_act_lds(uint8_t *smem) {
+    float *X = reinterpret_cast<float *>(smem);                       // [pol_x_rows][65]
+    float *P = X + pol_x_rows(K) * POL_LS;                            // [144][65]
+    return PolLds{X, P, X, P, X, P};
+}
+
 // ---- G: action_net and value_net on H2 = P, then the action choice and the outputs of sample b (= the lane's, if
 // `live`): wave 0 of mgx_policy_kernel and of mgx_policy_moe_kernel, one sample per lane.  b is the sample's position
 // in the caller's index: where its outputs go and what keys its draw.  read_ctr() loads the launch counter (mode 2
@@ -341,8 +395,7 @@ __device__ __forceinline__ void pol_l1(const float *__restrict__ W, int wv, int 
 template <int K, class ReadCtr>
 __device__ __forceinline__ unsigned long long pol_heads(const float *__restrict__ W, const float *P, int lane, bool live,
                                                         int64_t b, int mode, uint64_t seed, ReadCtr read_ctr,
-                                                        long long *actions, float *values, float *log_probs,
-                                                        float *logits) {
+                                                        const PolOut &out) {
     constexpr PolBlob L = pol_blob(K);
     constexpr int LS = POL_LS;
     float lg[POL_NA], val[1];
@@ -354,10 +407,10 @@ __device__ __forceinline__ unsigned long long pol_heads(const float *__restrict_
     unsigned long long c = 0;
     if (mode == 2) c = read_ctr();
     if (live) {
-        if (values) values[b] = val[0];
-        if (logits) {
+        if (out.values) out.values[b] = val[0];
+        if (out.logits) {
 #pragma unroll
-            for (int o = 0; o < POL_NA; o++) logits[b * POL_NA + o] = lg[o];
+            for (int o = 0; o < POL_NA; o++) out.logits[b * POL_NA + o] = lg[o];
         }
         if (mode != 0) {
             float mx = lg[0];
@@ -382,8 +435,8 @@ __device__ __forceinline__ unsigned long long pol_heads(const float *__restrict_
             float la = lg[0];
 #pragma unroll
             for (int o = 1; o < POL_NA; o++) la = act == o ? lg[o] : la;
-            actions[b] = act;
-            log_probs[b] = (la - mx) - logf(tot);
+            out.actions[b] = act;
+            out.log_probs[b] = (la - mx) - logf(tot);
         }
     }
     return c;
@@ -392,42 +445,20 @@ __device__ __forceinline__ unsigned long long pol_heads(const float *__restrict_
 template <int K>
 __global__ __launch_bounds__(POL_THREADS, 4) void mgx_policy_kernel(PolArgs a) {
     extern __shared__ __align__(16) uint8_t smem[];
-    constexpr int LS = POL_LS;
-    float *X = reinterpret_cast<float *>(smem);                       // [pol_x_rows][65]
-    float *P = X + pol_x_rows(K) * LS;                                // [144][65]
-    float *F = P;                                                     // [80][65], once the pooled maps are dead
     __shared__ const uint8_t *s_src[POL_TILE * K];
     __shared__ int s_mid[POL_TILE * K];                               // -1: empty slot
+    const PolLds r = pol_act_lds<K>(smem);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);          // wave-uniform: weight addresses stay scalar
     const int64_t b0 = (int64_t)blockIdx.x * POL_TILE;
     const int nb = (int)min<int64_t>(POL_TILE, a.s.B - b0);
     const float *__restrict__ W = a.blob;
-
-    pol_stage_src<K>(a.s, a.newest, b0, nb, tid, s_src, s_mid);       // A
-    __syncthreads();
-    pol_stage_rows<K>(s_src, tid, X);                                 // A2
-    int v;
-    const float *__restrict__ mf = a.mfeat + (size_t)pol_feat_row<K>(s_mid, lane, nb, v) * 128;
-    __syncthreads();
-    const uint8_t *xb = reinterpret_cast<const uint8_t *>(X) + lane * 4;
-    const uint32_t dsel = pol_dsel<K>(xb);
-    pol_conv1<K>(W, wv, lane, xb, P);                                 // B
-    __syncthreads();                                                  // rows dead from here: X becomes C2
-    pol_conv2<K>(W, wv, lane, P, X);                                  // C
-    __syncthreads();
-    pol_conv3_dir<K>(W, wv, lane, dsel, v, X, F);                     // D
-    __syncthreads();
-    pol_l0<K>(W, wv, lane, mf, F, X);                                 // E: H1 = X
-    __syncthreads();
-    pol_l1<K>(W, wv, lane, X, P);                                     // F: H2 = P
-    __syncthreads();
+    pol_trunk<K>(a.s, a.newest, b0, nb, tid, lane, wv, W, a.mfeat, s_src, s_mid, r, [](int) {});   // A to F
     // ---- G: heads, action choice and outputs: wave 0, one sample per lane
     if (wv != 0) return;
     const unsigned long long c = pol_heads<K>(
-        W, P, lane, lane < nb, b0 + lane, a.mode, a.seed,
-        [&] { return *reinterpret_cast<volatile unsigned long long *>(a.ctr); }, a.actions, a.values, a.log_probs,
-        a.logits);
+        W, r.H2, lane, lane < nb, b0 + lane, a.mode, a.seed,
+        [&] { return *reinterpret_cast<volatile unsigned long long *>(a.ctr); }, a.out);
     // the launch counter, as mgx_random_actions_kernel: every workgroup has read it (above, the whole wave) before its
     // own tally add; the last one to arrive advances it
     if (a.mode == 2 && tid == 0) {
@@ -443,8 +474,8 @@ __global__ __launch_bounds__(POL_THREADS, 4) void mgx_policy_kernel(PolArgs a) {
 // ---- mgx_policy_bootstrap: rewards[e] += gamma * V(terminal observation of e) for every env with truncated & !terminated
 // at one step, the work list built on the device (DESIGN.md "Graph-captured collect").  Two launches.
 struct PolBootArgs {
-    const uint8_t *rows, *mids, *starts;
-    int64_t N, R, row;                     // sample of env e: flat index row * N + e
+    SampleAddr s;                          // the buffer; index = the list, B unused (the count is on the device)
+    int64_t row;                           // sample of env e: flat index row * N + e
     const uint8_t *newest;                 // the terminal rows [N][FROW]
     const float *blob, *mfeat;
     const uint8_t *truncated, *terminated;
@@ -464,9 +495,9 @@ __global__ __launch_bounds__(BOOT_THREADS) void mgx_boot_list_kernel(PolBootArgs
     __shared__ int s_tot[NWV];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     int base = 0;                                                     // selected envs before this chunk (uniform)
-    for (int64_t e0 = 0; e0 < a.N; e0 += BOOT_THREADS) {
+    for (int64_t e0 = 0; e0 < a.s.N; e0 += BOOT_THREADS) {
         const int64_t e = e0 + tid;
-        const bool sel = e < a.N && a.truncated[e] != 0 && a.terminated[e] == 0;
+        const bool sel = e < a.s.N && a.truncated[e] != 0 && a.terminated[e] == 0;
         const unsigned long long m = __ballot(sel);
         if (lane == 0) s_tot[wv] = __popcll(m);
         __syncthreads();
@@ -477,14 +508,14 @@ __global__ __launch_bounds__(BOOT_THREADS) void mgx_boot_list_kernel(PolBootArgs
             before += w < wv ? c : 0;
             total += c;
         }
-        if (sel) a.list[base + before + __popcll(m & ((1ull << lane) - 1ull))] = a.row * a.N + e;
+        if (sel) a.list[base + before + __popcll(m & ((1ull << lane) - 1ull))] = a.row * a.s.N + e;
         base += total;
         __syncthreads();                                              // s_tot is rewritten by the next chunk
     }
     if (tid == 0) *a.count = base;
 }
 
-// Launch 2: the value pass over the list: mgx_policy_kernel's stages A to F and the value head on the terminal stack of
+// Launch 2: the value pass over the list: the forward pass (pol_trunk) and the value head on the terminal stack of
 // every listed sample, then rewards[e] = rewards[e] + gamma * v as two fp32 operations (what the eager index_put_ of
 // r[boot] + gamma * V computes).  The count is read from the device, so the grid is sized for the worst case, one
 // workgroup per tile of the N envs; a workgroup whose tile lies past the count exits after that one load, and with count
@@ -494,44 +525,25 @@ template <int K>
 __global__ __launch_bounds__(POL_THREADS, 4) void mgx_policy_boot_kernel(PolBootArgs a) {
     extern __shared__ __align__(16) uint8_t smem[];
     constexpr PolBlob L = pol_blob(K);
-    constexpr int LS = POL_LS;
-    float *X = reinterpret_cast<float *>(smem);                       // [pol_x_rows][65]
-    float *P = X + pol_x_rows(K) * LS;                                // [144][65]
-    float *F = P;
     __shared__ const uint8_t *s_src[POL_TILE * K];
     __shared__ int s_mid[POL_TILE * K];
+    const PolLds r = pol_act_lds<K>(smem);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const float *__restrict__ W = a.blob;
-    const int64_t cnt = min<int64_t>(*a.count, a.N);                  // (a list never holds more than N entries)
+    const int64_t cnt = min<int64_t>(*a.count, a.s.N);                // (a list never holds more than N entries)
     const int64_t b0 = (int64_t)blockIdx.x * POL_TILE;
     if (b0 >= cnt) return;                                            // the whole workgroup: no barrier is skipped
-    const SampleAddr s{a.rows, a.mids, a.starts, a.N, a.R, a.list, cnt};
+    SampleAddr s = a.s;                                               // the buffer, with the list as the index
+    s.index = a.list, s.B = cnt;
     const int nb = (int)min<int64_t>(POL_TILE, cnt - b0);
-    pol_stage_src<K>(s, a.newest, b0, nb, tid, s_src, s_mid);         // A
-    __syncthreads();
-    pol_stage_rows<K>(s_src, tid, X);                                 // A2
-    int v;
-    const float *__restrict__ mf = a.mfeat + (size_t)pol_feat_row<K>(s_mid, lane, nb, v) * 128;
-    __syncthreads();
-    const uint8_t *xb = reinterpret_cast<const uint8_t *>(X) + lane * 4;
-    const uint32_t dsel = pol_dsel<K>(xb);
-    pol_conv1<K>(W, wv, lane, xb, P);                                 // B
-    __syncthreads();
-    pol_conv2<K>(W, wv, lane, P, X);                                  // C
-    __syncthreads();
-    pol_conv3_dir<K>(W, wv, lane, dsel, v, X, F);                     // D
-    __syncthreads();
-    pol_l0<K>(W, wv, lane, mf, F, X);                                 // E
-    __syncthreads();
-    pol_l1<K>(W, wv, lane, X, P);                                     // F
-    __syncthreads();
+    pol_trunk<K>(s, a.newest, b0, nb, tid, lane, wv, W, a.mfeat, s_src, s_mid, r, [](int) {});     // A to F
     if (wv != 0) return;                                              // the value head: wave 0, one sample per lane
     float val[1];
     val[0] = W[L.vn_b];
-    pol_dot<1>(val, W + L.vn_w, 64, 64, pol_lds4(P + 64 * LS + lane));
+    pol_dot<1>(val, W + L.vn_w, 64, 64, pol_lds4(r.H2 + 64 * POL_LS + lane));
     if (lane < nb) {
-        const int64_t e = a.list[b0 + lane] % a.N;
+        const int64_t e = a.list[b0 + lane] % a.s.N;
         const float gv = __fmul_rn(a.gamma, val[0]);
         a.rewards[e] = __fadd_rn(a.rewards[e], gv);
         if (a.values) a.values[b0 + lane] = val[0];
@@ -554,8 +566,7 @@ struct PolMoeArgs {
     int *rec;                              // [MOE_REC]
     int64_t *list;                         // [n_samples + 63 n_experts]: SampleAddr.index of launch 2
     int *pos;                              // the same length: the position p of each list entry
-    long long *actions;
-    float *values, *log_probs, *logits;
+    PolOut out;
 };
 
 // Launch 1: a stable partition of the positions by expert, by ONE workgroup (mgx_boot_list_kernel's compaction, once
@@ -659,12 +670,9 @@ __global__ __launch_bounds__(MOE_THREADS) void mgx_moe_route_kernel(PolMoeArgs a
 template <int K>
 __global__ __launch_bounds__(POL_THREADS, 4) void mgx_policy_moe_kernel(PolMoeArgs a) {
     extern __shared__ __align__(16) uint8_t smem[];
-    constexpr int LS = POL_LS;
-    float *X = reinterpret_cast<float *>(smem);                       // [pol_x_rows][65]
-    float *P = X + pol_x_rows(K) * LS;                                // [144][65]
-    float *F = P;
     __shared__ const uint8_t *s_src[POL_TILE * K];
     __shared__ int s_mid[POL_TILE * K];
+    const PolLds r = pol_act_lds<K>(smem);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tile = (int)blockIdx.x;
@@ -681,30 +689,13 @@ __global__ __launch_bounds__(POL_THREADS, 4) void mgx_policy_moe_kernel(PolMoeAr
     nb = __builtin_amdgcn_readfirstlane(nb);
     const float *__restrict__ W = a.blob[e];
     const int64_t b0 = (int64_t)tile * POL_TILE;                      // the tile's first list slot
-    const SampleAddr s{a.s.rows, a.s.mids, a.s.starts, a.s.N, a.s.R, a.list, b0 + nb};
-    pol_stage_src<K>(s, a.newest, b0, nb, tid, s_src, s_mid);         // A
-    __syncthreads();
-    pol_stage_rows<K>(s_src, tid, X);                                 // A2
-    int v;
-    const float *__restrict__ mf = a.mfeat[e] + (size_t)pol_feat_row<K>(s_mid, lane, nb, v) * 128;
-    __syncthreads();
-    const uint8_t *xb = reinterpret_cast<const uint8_t *>(X) + lane * 4;
-    const uint32_t dsel = pol_dsel<K>(xb);
-    pol_conv1<K>(W, wv, lane, xb, P);                                 // B
-    __syncthreads();
-    pol_conv2<K>(W, wv, lane, P, X);                                  // C
-    __syncthreads();
-    pol_conv3_dir<K>(W, wv, lane, dsel, v, X, F);                     // D
-    __syncthreads();
-    pol_l0<K>(W, wv, lane, mf, F, X);                                 // E
-    __syncthreads();
-    pol_l1<K>(W, wv, lane, X, P);                                     // F
-    __syncthreads();
+    SampleAddr s = a.s;                                               // the buffer, with the partition as the index
+    s.index = a.list, s.B = b0 + nb;
+    pol_trunk<K>(s, a.newest, b0, nb, tid, lane, wv, W, a.mfeat[e], s_src, s_mid, r, [](int) {});  // A to F
     if (wv != 0) return;                                              // G: wave 0; outputs and the draw's key at p
     const int64_t p = lane < nb ? a.pos[b0 + lane] : 0;
-    pol_heads<K>(W, P, lane, lane < nb, p, a.mode, a.seed,
-                 [&] { return *reinterpret_cast<const unsigned long long *>(a.rec + MOE_REC_CTR); }, a.actions,
-                 a.values, a.log_probs, a.logits);
+    pol_heads<K>(W, r.H2, lane, lane < nb, p, a.mode, a.seed,
+                 [&] { return *reinterpret_cast<const unsigned long long *>(a.rec + MOE_REC_CTR); }, a.out);
 }
 
 #endif  // MGX_POLICY_H_

@@ -7,7 +7,7 @@
 // into its own slab scratch[g][blob words] with plain loads and stores (the first tile stores, so the scratch need
 // not be zeroed); mgx_policy_fold_kernel then adds the slabs in group order: grad_blob is bitwise reproducible.
 // Three passes per tile:
-//   (a) forward   stages A-F of mgx_policy_kernel: the same pol_* functions (mgx_policy.h) with this kernel's LDS
+//   (a) forward   stages A-F of mgx_policy_kernel: the same pol_trunk (mgx_policy.h) with this kernel's six LDS
 //                 regions, every activation kept in LDS as [feature][sample], row stride 65 dwords
 //   (b) backward  lane = sample, waves split a layer's INPUTS: dX[i] = sum_o W[o][i] dZ[o] with wave-uniform scalar
 //                 weight loads, written in place over the activation it replaces (Tanh' and ReLU' from the outputs)
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(POL_THREADS, 2) void mgx_policy_grad_kernel(PolGrad
                 if (lane == 0) put(off + o, x);
             }
         };
-        // ---- A, A2: source row of every (sample, slot), then the rows -> Y (no terminal rows)
+        // ---- A, A2 again, for conv1's backward: source row of every (sample, slot), then the rows -> Y
         const auto stage_rows = [&]() {
             pol_stage_src<K>(a.s, nullptr, b0, nb, tid, s_src, s_mid);
             __syncthreads();
@@ -117,40 +117,30 @@ __global__ __launch_bounds__(POL_THREADS, 2) void mgx_policy_grad_kernel(PolGrad
         };
         const uint8_t *xb = reinterpret_cast<const uint8_t *>(Y) + lane * 4;
 
-        // =============================================================== (a) forward: mgx_policy.h's stages
-        stage_rows();
-        for (int i = tid; i < 8 * POL_TILE; i += POL_THREADS) {      // the cotangents; spare lanes: exactly zero
-            const int o = i >> 6, s = i & 63;
-            float g = 0.0f;
-            if (s < nb) g = o < POL_NA ? a.g_logits[(b0 + s) * POL_NA + o] : a.g_values[b0 + s];
-            s_g[o * LS + s] = g;
-        }
-        int v;
-        const int my_key = pol_feat_row<K>(s_mid, lane, nb, v);
-        const float *__restrict__ mf = a.mfeat + (size_t)my_key * 128;
-        if (wv == 0) {                                                // a key's first sample leads its table sum
-            const int kreg = lane < nb ? my_key : -1;
-            bool lead = lane < nb;
-            for (int q = 0; q < POL_TILE - 1; q++) {
-                const int kq = __shfl(kreg, q, 64);
-                if (q < lane && kq == kreg) lead = false;
+        // =============================================================== (a) forward: mgx_policy.h's pol_trunk, no
+        // terminal rows; the rows lie over C2.  Beside the rows it stages the cotangents and the table keys
+        const PolLane pl = pol_trunk<K>(a.s, nullptr, b0, nb, tid, lane, wv, W, a.mfeat, s_src, s_mid,
+                                        PolLds{Y, P, C2, F, H1, H2}, [&](int my_key) {
+            for (int i = tid; i < 8 * POL_TILE; i += POL_THREADS) {  // the cotangents; spare lanes: exactly zero
+                const int o = i >> 6, s = i & 63;
+                float g = 0.0f;
+                if (s < nb) g = o < POL_NA ? a.g_logits[(b0 + s) * POL_NA + o] : a.g_values[b0 + s];
+                s_g[o * LS + s] = g;
             }
-            const unsigned long long leaders = __ballot(lead);
-            s_key[lane] = kreg;
-            s_lead[lane] = lead ? __popcll(leaders & ((1ull << lane) - 1ull)) : -1;
-        }
-        __syncthreads();
-        const uint32_t dsel = pol_dsel<K>(xb);
-        pol_conv1<K>(W, wv, lane, xb, P);                             // B
-        __syncthreads();                                              // rows dead: Y becomes C2
-        pol_conv2<K>(W, wv, lane, P, C2);                             // C
-        __syncthreads();
-        pol_conv3_dir<K>(W, wv, lane, dsel, v, C2, F);                // D
-        __syncthreads();
-        pol_l0<K>(W, wv, lane, mf, F, H1);                            // E
-        __syncthreads();
-        pol_l1<K>(W, wv, lane, H1, H2);                               // F
-        __syncthreads();
+            if (wv == 0) {                                            // a key's first sample leads its table sum
+                const int kreg = lane < nb ? my_key : -1;
+                bool lead = lane < nb;
+                for (int q = 0; q < POL_TILE - 1; q++) {
+                    const int kq = __shfl(kreg, q, 64);
+                    if (q < lane && kq == kreg) lead = false;
+                }
+                const unsigned long long leaders = __ballot(lead);
+                s_key[lane] = kreg;
+                s_lead[lane] = lead ? __popcll(leaders & ((1ull << lane) - 1ull)) : -1;
+            }
+        });
+        const int v = pl.v;
+        const uint32_t dsel = pl.dsel;
 
         // =============================================================== (b), (c) backward, heads first
         // ---- heads: dWa[o][i] = sum_s g[o][s] H2p[i][s], dWvn[i] = sum_s gv[s] H2v[i][s]; biases = row sums of g

@@ -187,7 +187,8 @@ class ExpertActor:
     evaluate_policy(expert, engine, n, fused=expert) and GraphEvaluator(expert) run it unchanged -- but it acts on the
     engine's CURRENT state, not on rows of a buffer: `t` must be the buffer's newest observation.  That is checked
     where the host can see it (act(): the buffer's rollout position against the engine's call count); _run, which
-    gets bare indices, only checks the buffer's engine.  last_cost: the cost tensor (i32 [N]) of the last call."""
+    gets bare indices, only checks the buffer's engine.  last_cost: the cost tensor (i32 [N]) of the last call.
+    A duck type, not a CompactActor: it has no values or logits, and its act reads no rows."""
 
     def __init__(self, engine):
         import torch

@@ -162,61 +162,34 @@ def fill_policy(p, blob, mission_feat, mode, seed=0, counter=None):
     return p
 
 
-def policy_act(engine, buf, index, p, o, values, actions=None, log_probs=None, logits=None, terminal=False):
-    """mgx_policy_act on the samples `index` (i64, contiguous) of `buf`; p: the MgxPolicy as fill_policy left it; o: the
-    MgxActOut to fill.  actions i64 [n] and log_probs f32 [n] only in modes 1 and 2; logits f32 [n, 7] optional."""
-    n, dev, f32 = index.numel(), engine.device, torch.float32
+def fill_act_out(o, engine, n, mode, values, actions=None, log_probs=None, logits=None):
+    """Fill the MgxActOut `o` with the checked outputs of n samples: values f32 [n]; actions i64 [n] and log_probs
+    f32 [n] only in modes 1 and 2; logits f32 [n, 7] optional."""
+    dev, f32 = engine.device, torch.float32
     o.actions_dev = o.log_probs_dev = o.logits_dev = None
     o.values_dev = _lib.check_tensor(values, "values", f32, n, dev).data_ptr()
-    if p.mode:
+    if mode:
         o.actions_dev = _lib.check_tensor(actions, "actions", torch.int64, n, dev).data_ptr()
         o.log_probs_dev = _lib.check_tensor(log_probs, "log_probs", f32, n, dev).data_ptr()
     if logits is not None:
         o.logits_dev = _lib.check_tensor(logits, "logits", f32, n * N_ACTIONS, dev).data_ptr()
+    return o
+
+
+def policy_act(engine, buf, index, p, o, values, actions=None, log_probs=None, logits=None, terminal=False):
+    """mgx_policy_act on the samples `index` (i64, contiguous) of `buf`; p: the MgxPolicy as fill_policy left it; o: the
+    MgxActOut to fill (fill_act_out)."""
+    fill_act_out(o, engine, index.numel(), p.mode, values, actions, log_probs, logits)
     _lib.check(engine.L.mgx_policy_act(*sample_addr(engine, buf, index, bool(terminal)), ctypes.byref(p),
                                        ctypes.byref(o), engine._stream()), "mgx_policy_act")
 
 
-class FusedActor:
-    """actions / values / log-probs of `policy` for observations of a CompactBuffer of `engine`, one launch each."""
+class CompactActor:
+    """What the actors over compact rows share: act / values / logits for observations of a CompactBuffer of
+    self.engine.  A subclass enqueues its kernels in _launch(buf, idx, mode, values, actions, log_probs, lg,
+    terminal): idx i64 contiguous and not empty, the other tensors as fill_act_out takes them."""
 
-    def __init__(self, policy, engine, seed=0, fused_mission=False):
-        k, _ = _params(policy)                       # ValueError before anything touches the device
-        if engine is None or k != engine.n_stack:
-            raise ValueError("policy n_stack %d does not match the engine's" % k)
-        self.policy, self.engine = policy, engine
-        self.K = k
-        self.seed = int(seed) & (2 ** 64 - 1)
-        dev = engine.device
-        words = library_blob_words(engine, k)
-        self.blob = torch.zeros(words, dtype=torch.float32, device=dev)
-        self.mission_feat = torch.zeros((256, k, 128), dtype=torch.float32, device=dev)
-        self.counter = torch.zeros(2, dtype=torch.int64, device=dev)      # u64 [2] (mgx_random_actions' contract)
-        self._tokens = _lib.mission_tokens()
-        self.mission = self._stacks = None
-        if fused_mission:                            # the table through mgx_mission_forward (mgx/fused_mission.py)
-            from .fused_mission import FusedMissionEncoder
-            self.mission = FusedMissionEncoder(policy, dev)
-            self._stacks = mission_token_stacks(k, self._tokens).reshape(256 * k, 32 * k).to(torch.uint8).to(dev)
-        self._pol = _lib.MgxPolicy()
-        self._out = _lib.MgxActOut()
-        self._boot = _lib.MgxBootstrap()
-        self.boot_list = torch.zeros(engine.n, dtype=torch.int64, device=dev)     # bootstrap()'s device work list
-        self.boot_count = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._table = None                          # index_table()
-        self.sync()
-
-    @torch.no_grad()
-    def sync(self):
-        """Repack the blob and rebuild the mission-feature table from the policy's current parameters."""
-        was = self.policy.training
-        self.policy.train(False)
-        self.blob.copy_(pack_blob(self.policy))
-        if self.mission is not None:
-            self.mission_feat.copy_(self.mission.encode(self._stacks).reshape(256, self.K, 128))
-        else:
-            self.mission_feat.copy_(mission_table(self.policy, self._tokens))
-        self.policy.train(was)
+    _table = None                                   # index_table()
 
     def _run(self, buf, index, mode, terminal=False, logits=False, out=None):
         """out: (actions, values, log_probs) tensors the kernel writes instead of fresh ones (actions and log_probs
@@ -235,8 +208,7 @@ class FusedActor:
             log_probs = torch.empty(n, **f32) if mode else None
         lg = torch.empty((n, N_ACTIONS), **f32) if logits else None
         if n:
-            p = fill_policy(self._pol, self.blob, self.mission_feat, mode, self.seed, self.counter)
-            policy_act(e, buf, idx, p, self._out, values, actions, log_probs, lg, terminal=terminal)
+            self._launch(buf, idx, mode, values, actions, log_probs, lg, terminal)
         return actions, values, log_probs, lg
 
     def index_table(self, buf):
@@ -265,6 +237,56 @@ class FusedActor:
         return self._run(buf, self._index(buf, t, envs), 0, terminal=terminal,
                          out=None if out is None else (None, out, None))[1]
 
+    def logits(self, buf, t, terminal=False, envs=None):
+        """(logits f32 [N, 7], values f32 [N]) of observation t (tests)."""
+        _, v, _, lg = self._run(buf, self._index(buf, t, envs), 0, terminal=terminal, logits=True)
+        return lg, v
+
+
+class FusedActor(CompactActor):
+    """actions / values / log-probs of `policy` for observations of a CompactBuffer of `engine`, one launch each."""
+
+    def __init__(self, policy, engine, seed=0, fused_mission=False):
+        k, _ = _params(policy)                       # ValueError before anything touches the device
+        if engine is None or k != engine.n_stack:
+            raise ValueError("policy n_stack %d does not match the engine's" % k)
+        self.policy, self.engine = policy, engine
+        self.K = k
+        self.seed = int(seed) & (2 ** 64 - 1)
+        dev = engine.device
+        words = library_blob_words(engine, k)
+        self.blob = torch.zeros(words, dtype=torch.float32, device=dev)
+        self.mission_feat = torch.zeros((256, k, 128), dtype=torch.float32, device=dev)
+        self.counter = torch.zeros(2, dtype=torch.int64, device=dev)      # u64 [2] (mgx_random_actions' contract)
+        self._tokens = _lib.mission_tokens()
+        self.mission = self._stacks = None
+        if fused_mission:                            # the table through mgx_mission_forward (mgx/fused_mission.py)
+            from .fused_mission import FusedMissionEncoder
+            self.mission = FusedMissionEncoder(policy, dev)
+            self._stacks = mission_token_stacks(k, self._tokens).reshape(256 * k, 32 * k).to(torch.uint8).to(dev)
+        self._pol = _lib.MgxPolicy()
+        self._out = _lib.MgxActOut()
+        self._boot = _lib.MgxBootstrap()
+        self.boot_list = torch.zeros(engine.n, dtype=torch.int64, device=dev)     # bootstrap()'s device work list
+        self.boot_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.sync()
+
+    @torch.no_grad()
+    def sync(self):
+        """Repack the blob and rebuild the mission-feature table from the policy's current parameters."""
+        was = self.policy.training
+        self.policy.train(False)
+        self.blob.copy_(pack_blob(self.policy))
+        if self.mission is not None:
+            self.mission_feat.copy_(self.mission.encode(self._stacks).reshape(256, self.K, 128))
+        else:
+            self.mission_feat.copy_(mission_table(self.policy, self._tokens))
+        self.policy.train(was)
+
+    def _launch(self, buf, idx, mode, values, actions, log_probs, lg, terminal):
+        p = fill_policy(self._pol, self.blob, self.mission_feat, mode, self.seed, self.counter)
+        policy_act(self.engine, buf, idx, p, self._out, values, actions, log_probs, lg, terminal=terminal)
+
     def bootstrap(self, buf, t, gamma, rewards=None, values=None):
         """SB3's truncation bootstrap of step t on the device (mgx_policy_bootstrap): rewards[e] = rewards[e] +
         f32(gamma) * V(terminal observation of e) for every env with truncated & ~terminated at step t, in place in
@@ -289,8 +311,3 @@ class FusedActor:
                                             P(buf.terminal_rows.data_ptr()), ctypes.byref(p), ctypes.byref(b),
                                             e._stream()), "mgx_policy_bootstrap")
         return r
-
-    def logits(self, buf, t, terminal=False, envs=None):
-        """(logits f32 [N, 7], values f32 [N]) of observation t (tests)."""
-        _, v, _, lg = self._run(buf, self._index(buf, t, envs), 0, terminal=terminal, logits=True)
-        return lg, v

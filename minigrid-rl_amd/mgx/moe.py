@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .fused_policy import N_ACTIONS, FusedActor, _params, sample_addr
+from .fused_policy import CompactActor, FusedActor, _params, fill_act_out, sample_addr
 
 MAX_EXPERTS = _lib.MOE_MAX_EXPERTS
 RECORD_WORDS = _lib.MOE_RECORD_WORDS
@@ -165,18 +165,13 @@ def scratch_views(scratch, n_samples, n_experts):
     return rec, lst, scratch[RECORD_WORDS + 2 * cap:RECORD_WORDS + 3 * cap]
 
 
-class FusedMoEActor:
+class FusedMoEActor(CompactActor):
     """FusedActor for a MoEPolicy: actions / values / log-probs of the mixture for observations of a CompactBuffer
     of `engine`, two launches each (the route, the policy pass).  Per sample bit-equal to the routed expert's own
-    FusedActor at the same seed and counter.  engine, policy (= moe), sync, act, values, logits, _run, index_table
-    and counter are FusedActor's; there is no bootstrap.  After a call `last_route` (i32 [32], the record of
-    include/mgx.h) holds (start, count) per expert, the live tile count and the unroutable count."""
-
-    index_table = FusedActor.index_table
-    _index = FusedActor._index
-    act = FusedActor.act
-    values = FusedActor.values
-    logits = FusedActor.logits
+    FusedActor at the same seed and counter.  act, values, logits, _run and index_table are CompactActor's, as
+    FusedActor's are; engine, policy (= moe), sync and counter are as FusedActor's; there is no bootstrap.  After a
+    call `last_route` (i32 [32], the record of include/mgx.h) holds (start, count) per expert, the live tile count
+    and the unroutable count."""
 
     def __init__(self, moe, engine, seed=0, fused_mission=False):
         if not isinstance(moe, MoEPolicy):
@@ -195,7 +190,6 @@ class FusedMoEActor:
         self.route = torch.zeros(256, dtype=torch.uint8, device=dev)
         self._pol = _lib.MgxPolicyMoe()
         self._out = _lib.MgxActOut()
-        self._table = None
         self._n = 0
         self._reserve(engine.n)
         self.sync(experts=False)
@@ -219,43 +213,20 @@ class FusedMoEActor:
                 a.sync()
         self.route.copy_(check_route(self.policy.route, self.E))
 
-    def _run(self, buf, index, mode, terminal=False, logits=False, out=None):
-        """FusedActor._run's contract."""
-        e = self.engine
-        if buf.engine is not e:
-            raise ValueError("the buffer belongs to another engine")
-        idx = index.to(torch.int64).contiguous()
-        n = idx.numel()
-        f32 = dict(dtype=torch.float32, device=e.device)
-        if out is not None:
-            actions, values, log_probs = out
-        else:
-            values = torch.empty(n, **f32)
-            actions = torch.empty(n, dtype=torch.int64, device=e.device) if mode else None
-            log_probs = torch.empty(n, **f32) if mode else None
-        lg = torch.empty((n, N_ACTIONS), **f32) if logits else None
-        if n:
-            self._reserve(n)
-            p = self._pol
-            p.n_experts, p.mode, p.seed = self.E, int(mode), self.seed
-            for x, a in enumerate(self.experts):
-                p.blob_dev[x], p.mission_feat_dev[x] = a.blob.data_ptr(), a.mission_feat.data_ptr()
-            p.route_dev, p.counter_dev = self.route.data_ptr(), self.counter.data_ptr()
-            p.scratch_dev, p.scratch_words = self.scratch.data_ptr(), self.scratch.numel()
-            moe_act(e, buf, idx, p, self._out, values, actions, log_probs, lg, terminal=terminal)
-        return actions, values, log_probs, lg
+    def _launch(self, buf, idx, mode, values, actions, log_probs, lg, terminal):
+        self._reserve(idx.numel())
+        p = self._pol
+        p.n_experts, p.mode, p.seed = self.E, int(mode), self.seed
+        for x, a in enumerate(self.experts):
+            p.blob_dev[x], p.mission_feat_dev[x] = a.blob.data_ptr(), a.mission_feat.data_ptr()
+        p.route_dev, p.counter_dev = self.route.data_ptr(), self.counter.data_ptr()
+        p.scratch_dev, p.scratch_words = self.scratch.data_ptr(), self.scratch.numel()
+        moe_act(self.engine, buf, idx, p, self._out, values, actions, log_probs, lg, terminal=terminal)
 
 
 def moe_act(engine, buf, index, p, o, values, actions=None, log_probs=None, logits=None, terminal=False):
     """mgx_policy_act_moe on the samples `index` (i64, contiguous) of `buf`; p: a filled MgxPolicyMoe; o: the
     MgxActOut to fill (policy_act's contract)."""
-    n, dev, f32 = index.numel(), engine.device, torch.float32
-    o.actions_dev = o.log_probs_dev = o.logits_dev = None
-    o.values_dev = _lib.check_tensor(values, "values", f32, n, dev).data_ptr()
-    if p.mode:
-        o.actions_dev = _lib.check_tensor(actions, "actions", torch.int64, n, dev).data_ptr()
-        o.log_probs_dev = _lib.check_tensor(log_probs, "log_probs", f32, n, dev).data_ptr()
-    if logits is not None:
-        o.logits_dev = _lib.check_tensor(logits, "logits", f32, n * N_ACTIONS, dev).data_ptr()
+    fill_act_out(o, engine, index.numel(), p.mode, values, actions, log_probs, logits)
     _lib.check(engine.L.mgx_policy_act_moe(*sample_addr(engine, buf, index, bool(terminal)), ctypes.byref(p),
                                            ctypes.byref(o), engine._stream()), "mgx_policy_act_moe")

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Two builds of libmgx.so against each other on the fused policy path: exact bits and speed.
 
-A refactor of the kernels behind mgx_gather_ring, mgx_policy_act and mgx_policy_backward must change neither a bit
-of what they compute nor their speed.  Build the parent commit's library to a second path (`make OUT=...`) and run
+A refactor of the kernels behind mgx_gather_ring, mgx_policy_act, mgx_policy_bootstrap, mgx_policy_act_moe and
+mgx_policy_backward must change neither a bit of what they compute nor their speed.  Build the parent commit's library to a second path (`make OUT=...`) and run
   python tools/ab_policy_libs.py --parent PATH/libmgx_parent.so [--new minigrid-rl_amd/mgx/libmgx.so] [--out DIR]
 Each library is loaded through MGX_LIB_PATH in child processes of its own, every child under its own time limit;
 the first failure ends the run.
@@ -10,10 +10,17 @@ the first failure ends the run.
 bits  tests/test_fused_policy_gpu.py's fixture (70 envs, a ring of 3 rows, 40 random steps; seeded, so both children
       see the same buffer) at n_stack 1, 4, 5, 8 x without / with terminal rows x 1, 64, 65, 200 samples: the gather's
       image, direction and mission in u8 and f32; mgx_policy_act's logits and values (mode 0), actions and log-probs
-      (mode 1, and mode 2 with one seed and a zeroed counter); mgx_policy_backward's grad_blob at max_groups 2, and
-      grad_mission_feat where the samples fit one tile (<= 64: across tiles its atomic order is run-dependent even
-      for one library).  Compared byte for byte -> OUT/bits.json; any differing tensor makes the run fail.
+      (mode 1, and mode 2 with one seed and a zeroed counter); mgx_policy_act_moe's the same in the three modes and
+      words 0..17 of its route record, for mixtures of 1 and 4 experts (mission id m -> expert m % E);
+      mgx_policy_backward's grad_blob at max_groups 2, and grad_mission_feat where the samples fit one tile (<= 64:
+      across tiles its atomic order is run-dependent even for one library).  Per n_stack also mgx_policy_bootstrap
+      of the fixture's last step: the rewards, the list, the count and the values.  Random actions end this
+      fixture's episodes long before max_steps, so no step of it truncates an env: the step's flags are drawn from
+      the seeded generator (truncated for half of the envs, terminated for a quarter) and the terminal rows are
+      random bytes, as tests/test_graph_collect_gpu.py does; a count of 0 fails the child, the parent's counts are
+      recorded.  Compared byte for byte -> OUT/bits.json; any differing tensor makes the run fail.
 time  config 3's env, 65,536 envs, n_stack 4: FusedActor.act, FusedEvaluator.forward_raw and backward_raw (+ fold),
+      FusedMoEActor.act (4 experts) and FusedActor.bootstrap (every 4th env flagged truncated),
       device events after a warm-up, 20 repeats per child; children in the order parent, new, parent, new, so that
       the parent's spread over two loads of the same library is measured in the same run.  Per timing: the medians
       and ranges of every child and of each library's 40 pooled repeats; `within_parent_range` = the new library's
@@ -39,7 +46,9 @@ ENV3 = dict(problem="multi", mission=2, size=8, num_objects=4)
 FIXTURE = dict(problem="gtg", mission=5, size=6, num_objects=2)      # tests/test_fused_policy_gpu.py: ENV
 N_ENVS, T_RING, STEPS = 70, 3, 40
 STACKS, COUNTS, MAX_GROUPS = (1, 4, 5, 8), (1, 64, 65, 200), 2
-TIMINGS = ("act", "forward_raw", "backward_raw_and_fold")
+EXPERTS = (1, 4)                                                     # mixtures; mission id m goes to expert m % E
+GAMMA = 0.99
+TIMINGS = ("act", "forward_raw", "backward_raw_and_fold", "moe_act", "bootstrap")
 
 
 def _stat(ms):
@@ -63,13 +72,17 @@ def part_bits(args):
     from mgx.compact import CompactBuffer
     from mgx.fused_policy import FusedActor
     from mgx.fused_train import FusedEvaluator
-    out = {}
+    from mgx.moe import FusedMoEActor, MoEPolicy
+    out, counts = {}, {}
     for k in STACKS:
         pol = T._policy(k).cuda()
         eng = MgxEngine(n_envs=N_ENVS, n_stack=k, terminal_mode="truncated", mission_dtype=torch.uint8, **FIXTURE)
         buf = CompactBuffer(eng, T_RING, ring=True)
         actor = FusedActor(pol, eng, seed=1234)
         ev = FusedEvaluator(pol, eng, max_groups=MAX_GROUPS)
+        experts = [pol] + [T._policy(k, seed).cuda() for seed in range(1, max(EXPERTS))]
+        mixtures = {n_exp: FusedMoEActor(MoEPolicy(experts[:n_exp], torch.arange(256) % n_exp), eng, seed=1234)
+                    for n_exp in EXPERTS}
         eng.reset()
         buf.observe(0)
         g = torch.Generator().manual_seed(5)
@@ -97,14 +110,39 @@ def part_bits(args):
                 actor.counter.zero_()
                 a2, _, lp2, _ = actor._run(buf, index, 2, terminal=term)
                 out[tag + "mode2_actions"], out[tag + "mode2_log_probs"] = a2, lp2
+                for n_exp, mix in mixtures.items():
+                    mtag = tag + "moe%d_" % n_exp
+                    _, values, _, logits = mix._run(buf, index, 0, terminal=term, logits=True)
+                    out[mtag + "mode0_logits"], out[mtag + "mode0_values"] = logits, values
+                    out[mtag + "route_record"] = mix.last_route[:18].clone()
+                    a1, _, lp1, _ = mix._run(buf, index, 1, terminal=term)
+                    out[mtag + "mode1_actions"], out[mtag + "mode1_log_probs"] = a1, lp1
+                    mix.counter.zero_()
+                    a2, _, lp2, _ = mix._run(buf, index, 2, terminal=term)
+                    out[mtag + "mode2_actions"], out[mtag + "mode2_log_probs"] = a2, lp2
             tag = "k%d/n%d/" % (k, n)
             gb, gm = ev.backward_raw(buf, index, actor.blob, actor.mission_feat, gl, gv)
             out[tag + "grad_blob"] = gb
             if n <= 64:
                 out[tag + "grad_mission_feat"] = gm
+        # the bootstrap of the last step (last, because it draws the step's flags and the terminal rows)
+        buf.truncated[t - 1].copy_(torch.rand(N_ENVS, generator=g) < 0.5)
+        buf.terminated[t - 1].copy_(torch.rand(N_ENVS, generator=g) < 0.25)
+        rows = torch.randint(0, 256, buf.terminal_rows.shape, generator=g).to(torch.uint8)
+        rows[:, 0] %= 4
+        buf.terminal_rows.copy_(rows)
+        rew, val = torch.linspace(-1.0, 1.0, N_ENVS).cuda(), torch.full((N_ENVS,), 7.0).cuda()
+        actor.boot_list.fill_(-1)
+        actor.bootstrap(buf, t - 1, GAMMA, rewards=rew, values=val)
+        counts[k] = int(actor.boot_count)
+        if not 0 < counts[k] < N_ENVS:
+            raise SystemExit("bootstrap: %d of %d envs selected" % (counts[k], N_ENVS))
+        tag = "k%d/bootstrap/" % k
+        out[tag + "rewards"], out[tag + "values"] = rew, val
+        out[tag + "list"], out[tag + "count"] = actor.boot_list.clone(), actor.boot_count.clone()
         eng.poll_error()
     np.savez(args.save, **{name: v.cpu().numpy() for name, v in out.items()})
-    return dict(tensors=len(out))
+    return dict(tensors=len(out), bootstrap_counts=counts)
 
 
 def part_time(args):
@@ -113,6 +151,7 @@ def part_time(args):
     from mgx.compact import CompactBuffer
     from mgx.fused_policy import FusedActor
     from mgx.fused_train import FusedEvaluator
+    from mgx.moe import FusedMoEActor, MoEPolicy
     from mgx.policy import ActorCriticPolicy
     n, k = args.envs, 4
     torch.manual_seed(0)
@@ -128,9 +167,16 @@ def part_time(args):
     ev = FusedEvaluator(pol, eng)
     index = buf.index(8, buf._arange).to(torch.int64).contiguous()
     gl, gv = torch.randn((n, 7), device=eng.device), torch.randn(n, device=eng.device)
+    experts = [pol] + [ActorCriticPolicy(n_stack=k, mission_cache=True).to(eng.device) for _ in range(3)]
+    mix = FusedMoEActor(MoEPolicy(experts, torch.arange(256) % 4), eng, seed=1)
+    buf.truncated[7].copy_(torch.arange(n, device=eng.device) % 4 == 0)        # the bootstrap's work: every 4th env
+    buf.terminated[7].zero_()
+    rew = torch.zeros(n, device=eng.device)
     fns = dict(act=lambda: actor.act(buf, 8),
                forward_raw=lambda: ev.forward_raw(buf, index, actor.blob, actor.mission_feat),
-               backward_raw_and_fold=lambda: ev.backward_raw(buf, index, actor.blob, actor.mission_feat, gl, gv))
+               backward_raw_and_fold=lambda: ev.backward_raw(buf, index, actor.blob, actor.mission_feat, gl, gv),
+               moe_act=lambda: mix.act(buf, 8),
+               bootstrap=lambda: actor.bootstrap(buf, 7, GAMMA, rewards=rew))
     for _ in range(5):
         for fn in fns.values():
             fn()
@@ -170,7 +216,7 @@ def _train(args, torch):
     return ms
 
 
-PARTS = {"bits": (part_bits, 420), "time": (part_time, 540)}
+PARTS = {"bits": (part_bits, 540), "time": (part_time, 540)}
 
 
 def _child(args, part, lib, extra):
@@ -219,9 +265,12 @@ def main():
     if args.only in (None, "bits"):
         import numpy as np
         with tempfile.TemporaryDirectory() as tmp:
+            counts = {}
             for name, path in libs.items():
-                if _child(args, "bits", path, ["--save", os.path.join(tmp, name + ".npz")]) is None:
+                r = _child(args, "bits", path, ["--save", os.path.join(tmp, name + ".npz")])
+                if r is None:
                     return 1
+                counts[name] = r["bootstrap_counts"]
             a, b = (np.load(os.path.join(tmp, name + ".npz")) for name in ("parent", "new"))
             names = sorted(a.files)
             differing = [nm for nm in names if nm not in b.files or a[nm].dtype != b[nm].dtype or
@@ -229,7 +278,9 @@ def main():
             differing += [nm for nm in b.files if nm not in a.files]
         _write(os.path.join(args.out, "bits.json"),
                dict(meta, fixture=dict(FIXTURE, n_envs=N_ENVS, ring_rows=T_RING, steps=STEPS), n_stack=list(STACKS),
-                    sample_counts=list(COUNTS), max_groups=MAX_GROUPS, tensors_compared=len(names),
+                    sample_counts=list(COUNTS), max_groups=MAX_GROUPS, experts=list(EXPERTS),
+                    bootstrap=dict(gamma=GAMMA, parent_count_by_n_stack=counts["parent"]),
+                    tensors_compared=len(names),
                     tensors_differing=differing, bitwise_equal=not differing))
         print("bits: %d tensors compared, %d differ %s" % (len(names), len(differing), differing[:10]))
         ok = ok and not differing
