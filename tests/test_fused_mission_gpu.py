@@ -8,7 +8,14 @@ The Embedding and GRU parameters are redrawn (weights N(0, 1) / sqrt(fan-in), bi
 Shapes: seq_len 32, 128 and 256 (n_stack 1, 4, 8) at n_rows 1 and one below, at and one above the kernel's tile of
 3 rows per workgroup, and seq_len 32 at 256 rows (86 workgroups, the last one with a single live row).  Token sets:
 real (mission id, v) stacks, uniform random tokens covering all 32 values, all zeros; from two rows on the three are
-mixed in one input as well."""
+mixed in one input as well.
+
+Those shapes leave paths of the weight-gradient kernels unrun (their chunks are 32, 48 or 64 pairs long and at most
+152).  mission_ref.PLAN_SHAPES adds the shapes that run them -- seq_len 1, odd and unaligned seq_len, the tail loop of
+mgx_mission_wgrad_kernel with 1, 2 and 3 steps, a half-filled last step, the chunk count capped at 256 with chunks
+longer than 64 pairs and empty trailing chunks, 2,048 rows -- each named with its path there and checked against its
+derived plan by tests/test_fused_mission_cpu.py.  Same reference, same yardstick; tokens random / zero / alternating
+rows (mission_ref.plan_tokens: real stacks need seq_len to be a multiple of 32)."""
 import copy
 import math
 
@@ -16,6 +23,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+import mission_ref as R  # noqa: E402
 from mgx.policy import ActorCriticPolicy  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -42,16 +50,7 @@ def _ctx():
         return _CTX["c"]
     from mgx.fused_mission import FusedMissionEncoder, mission_params
     c = Ctx()
-    torch.manual_seed(0)
-    c.pol = ActorCriticPolicy(n_stack=4)
-    g = torch.Generator().manual_seed(77)
-    with torch.no_grad():
-        for t in mission_params(c.pol):
-            if t.dim() > 1:
-                t.copy_(torch.randn(t.shape, generator=g) / math.sqrt(t.shape[1]))
-            else:
-                t.copy_(0.5 * torch.randn(t.shape, generator=g))
-    c.pol = c.pol.cuda()
+    c.pol = R.redrawn_policy().cuda()
     c.pol.train(True)                      # MIOpen's RNN backward needs training mode
     c.seq32 = c.pol.features_extractor.extractors["mission"]
     c.seq64 = copy.deepcopy(c.seq32).cpu().double()
@@ -105,8 +104,8 @@ def _kernel(c, tokens, g, ws=None, params=None):
 
 
 def _bound_check(tag, got, ref, t32, need_signal=True):
-    """Every tensor of got within max(4 e_torch, 4 eps32 max|ref|) of ref; prints the ratios."""
-    bad = []
+    """Every tensor of got within max(4 e_torch, 4 eps32 max|ref|) of ref; prints the ratios.  -> {name: bound}"""
+    bad, bounds = [], {}
     for n in ref:
         e_torch = float((t32[n] - ref[n]).abs().max())
         scale = float(ref[n].abs().max())
@@ -116,9 +115,11 @@ def _bound_check(tag, got, ref, t32, need_signal=True):
               % (tag, n, dev, e_torch, bound, dev / bound if bound else float("inf")))
         if need_signal:
             assert scale > 0, n
+        bounds[n] = bound
         if not dev <= bound:
             bad.append((n, dev, bound))
     assert not bad, bad
+    return bounds
 
 
 _CASES = {}
@@ -165,6 +166,72 @@ def test_gradient_parity(seq, n_rows, kind):
     _bound_check("seq %d rows %d %s" % (seq, n_rows, kind), r.got[1], r.ref[1], r.t32[1])
 
 
+def _plan_case(n_rows, seq, kind):
+    """_case for a mission_ref.PLAN_SHAPES entry: mission_ref's tokens and cotangent."""
+    key = ("plan", seq, n_rows, kind)
+    if key in _CASES:
+        return _CASES[key]
+    c = _ctx()
+    r = Ctx()
+    r.tok, r.g = R.plan_tokens(kind, n_rows, seq), R.plan_cotangent(n_rows, seq)
+    r.ref = _module(c.seq64, r.tok.long(), r.g)
+    r.t32 = _module(c.seq32, r.tok.long().cuda(), r.g.cuda())
+    for p in c.seq32.parameters():
+        p.grad = None
+    r.got = _kernel(c, r.tok, r.g)
+    _CASES[key] = r
+    return r
+
+
+def _plan_gradient_check(n_rows, seq, kind):
+    """All five gradients of a plan case within the bound -> {name: bound}.  At seq_len 1 h_0 = 0 makes dW_hh zero:
+    exactly zero from the kernels, and the other four must carry signal."""
+    r = _plan_case(n_rows, seq, kind)
+    got, ref, t32 = (dict(d) for d in (r.got[1], r.ref[1], r.t32[1]))
+    if seq == 1:
+        assert not got.pop("w_hh").any() and not ref.pop("w_hh").any()
+        del t32["w_hh"]
+    return _bound_check("plan rows %d seq %d %s" % (n_rows, seq, kind), got, ref, t32)
+
+
+PLAN_PARITY = [(n, s, kind) for n, s in R.PLAN_SHAPES for kind in R.plan_kinds(n, s)]
+
+
+@pytest.mark.parametrize("n_rows,seq,kind", PLAN_PARITY)
+def test_forward_parity_plan_shapes(n_rows, seq, kind):
+    r = _plan_case(n_rows, seq, kind)
+    assert r.got[0].shape == (n_rows, 128) and torch.isfinite(r.got[0]).all()
+    _bound_check("plan rows %d seq %d %s" % (n_rows, seq, kind), {"features": r.got[0]}, {"features": r.ref[0]},
+                 {"features": r.t32[0]})
+
+
+@pytest.mark.parametrize("n_rows,seq,kind", PLAN_PARITY)
+def test_gradient_parity_plan_shapes(n_rows, seq, kind):
+    """All five gradients, N(0, 1) cotangent of the features, at the shapes that run the weight-gradient kernels'
+    tail loop, half-filled step, capped and empty chunks (mission_ref.PLAN_SHAPES names each shape's path)."""
+    _plan_gradient_check(n_rows, seq, kind)
+
+
+@pytest.mark.parametrize("n_rows,seq", R.PAIR_SHAPES)
+def test_single_pair_would_be_seen(n_rows, seq):
+    """A condition on the inputs that makes the parity test above a test of every (row, t) pair: by the explicit
+    fp64 GRU (mission_ref.gru_reference), each pair's own contribution to db_ih -- its (da_r, da_z, da_n) -- and, for
+    t > 0, to dW_hh -- its hidden-side cotangent (x) h_{t-1} -- has an entry above twice the bound the parity check
+    applies to that tensor in this run.  A pair dropped or taken twice at a chunk boundary, in the half-filled step
+    or in the tail loop then puts the gradient out of tolerance.  Random tokens; short seq_len only: over 64 steps
+    the cotangent decays too far ((9, 65) reaches 5.5 times the floor on the CPU), and the long shapes are left to
+    the parity test."""
+    c = _ctx()
+    bounds = _plan_gradient_check(n_rows, seq, "random")
+    r = _plan_case(n_rows, seq, "random")
+    ref = R.gru_reference(list(c.seq64.parameters()), r.tok, r.g)
+    for name, (small, floor) in R.pair_floor_ratios(ref).items():
+        print("plan rows %d seq %d %s: smallest pair contribution %.3e, bound %.3e (floor %.3e), factor %.1f"
+              % (n_rows, seq, name, small, bounds[name], floor, small / bounds[name]))
+        assert bounds[name] >= floor * (1.0 - 1e-12)
+        assert small > 2.0 * bounds[name], (name, small, bounds[name])
+
+
 @pytest.mark.parametrize("seq,n_rows", [(32, 1), (128, TILE + 1)])
 def test_unused_tokens_have_exactly_zero_embedding_gradient(seq, n_rows):
     """An input of tokens 0, 1 and 2 only: rows 3..31 of the Embedding gradient are exactly zero, rows 0..2 are
@@ -193,12 +260,15 @@ def test_token_values_are_masked():
     assert torch.equal(f0, f1) and all(torch.equal(g0[n], g1[n]) for n in NAMES)
 
 
-@pytest.mark.parametrize("seq,n_rows", [(128, 76), (32, TILE + 1)])
+@pytest.mark.parametrize("seq,n_rows", [(128, 76), (32, TILE + 1), (9, 1900), (256, 65)])
 def test_reproducible_and_workspace_independent(seq, n_rows):
     """Two runs are bitwise equal in the features and all five gradients; a workspace prefilled with NaN gives the
-    same bits (it need not be zeroed); the forward with and without a workspace gives the same features."""
+    same bits (it need not be zeroed); the forward with and without a workspace gives the same features.  At 1,900
+    x 9 and 65 x 256 the last 4 and 3 of the 256 chunks are empty: their slabs must come out as exact zeros, and no
+    masked-out operand may leak a NaN through 0 * NaN."""
     c = _ctx()
-    tok = _tokens("mixed", n_rows, seq, seed=1)
+    assert (R.chunk_plan(n_rows, seq)[4] > 0) == (n_rows * seq > 16384)
+    tok = _tokens("mixed", n_rows, seq, seed=1) if seq % 32 == 0 else R.plan_tokens("mixed", n_rows, seq, seed=1)
     g = torch.randn((n_rows, 128), generator=torch.Generator().manual_seed(5))
     f0, g0 = _kernel(c, tok, g)
     f1, g1 = _kernel(c, tok, g)

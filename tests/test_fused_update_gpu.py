@@ -249,7 +249,7 @@ LR, BETAS, ADAM_EPS = 3e-4, (0.9, 0.999), 1e-8
 
 def _adam_sizes():
     from mgx.fused_update import arena_layout
-    return (1, 63, 64, 65, 1025, arena_layout(4)[1])
+    return (1, 63, 64, 65, 1025, arena_layout(4)[1], 300001)   # the last: above 256 x 1,024 words, several per thread
 
 
 def _adam_inputs(n, target_norm):
@@ -347,7 +347,7 @@ def _adam_compare(n, case):
 
 
 @pytest.mark.parametrize("case", ["clip", "noclip", "off"])
-@pytest.mark.parametrize("size", range(6))
+@pytest.mark.parametrize("size", range(7))
 def test_adam_step_parity(size, case):
     """Three consecutive steps, each path carrying its own state: param, both moments, the written-back clipped
     gradient and the total norm after every step, with the clip active, inactive and switched off.  Two runs are
@@ -362,7 +362,7 @@ def test_adam_step_parity(size, case):
     assert not bad, bad
 
 
-@pytest.mark.parametrize("size", [0, 5])
+@pytest.mark.parametrize("size", [0, 5, 6])
 def test_adam_step_parity_resumed(size):
     """What a resumed run asks of mgx_adam_step: three steps from imported non-zero moments (exp_avg_sq >= 0) at
     step 12,345, against fp64 clip_grad_norm_ + torch.optim.Adam whose state was set to the same moments and step,
@@ -395,7 +395,7 @@ def test_adam_step_parity_resumed(size):
     assert not bad, bad
 
 
-@pytest.mark.parametrize("size", range(6))
+@pytest.mark.parametrize("size", range(7))
 def test_adam_grad_scale(size):
     """grad_scale = 0.5 equals pre-halved gradients with grad_scale = 1, bit for bit (halving is exact)."""
     _gpu()

@@ -145,9 +145,10 @@ def test_adam_step_sched_captured_graph_replays(n):
 
 
 # ---------------------------------------------------------------------------------------- mission _rows
-@pytest.mark.parametrize("n_rows,seq_len", [(1, 1), (5, 32), (76, 128), (33, 7)])
+@pytest.mark.parametrize("n_rows,seq_len", [(1, 1), (5, 32), (76, 128), (33, 7), (1900, 9)])
 def test_mission_rows_equal_forward_index_copy_and_index_select_backward(n_rows, seq_len):
-    """Shuffled, non-contiguous rows of a 1,024-row table pre-filled with a NaN-payload sentinel: the named rows are
+    """Shuffled, non-contiguous rows of a 1,024-row table (2 n_rows rows where that is more: 1,900 x 9 has the chunk
+    count capped and empty trailing chunks) pre-filled with a NaN-payload sentinel: the named rows are
     mgx_mission_forward's features, the others still hold the sentinel, the step records are the same; the five
     gradients equal mgx_mission_backward on the index_select-ed cotangent with every unnamed g_table row NaN."""
     _gpu()
@@ -159,23 +160,24 @@ def test_mission_rows_equal_forward_index_copy_and_index_select_backward(n_rows,
     params = tuple(p.detach().contiguous() for p in mission_params(pol))
     g = torch.Generator().manual_seed(100 * n_rows + seq_len)
     tokens = torch.randint(0, 32, (n_rows, seq_len), generator=g).to(torch.uint8).to(enc.device)
-    rows = torch.randperm(1024, generator=g)[:n_rows].to(enc.device)
+    table_rows = max(1024, 2 * n_rows)
+    rows = torch.randperm(table_rows, generator=g)[:n_rows].to(enc.device)
     words = int(enc.L.mgx_mission_workspace_words(n_rows, seq_len))
     ws_a = torch.zeros(words, device=enc.device)
     ws_b = torch.zeros(words, device=enc.device)
     sentinel = torch.tensor(SENTINEL, dtype=torch.int32).view(torch.float32).to(enc.device)
-    table = sentinel.expand(1024, 128).contiguous()
+    table = sentinel.expand(table_rows, 128).contiguous()
     feat = enc.forward_raw(tokens, params, ws_a)
     assert enc.forward_rows(tokens, params, table, rows, ws_b) is table
     torch.cuda.synchronize()
     assert torch.isfinite(feat).all() and feat.any()
     assert _same(table.index_select(0, rows), feat)
-    named = torch.zeros(1024, dtype=torch.bool, device=enc.device)
+    named = torch.zeros(table_rows, dtype=torch.bool, device=enc.device)
     named[rows] = True
     assert bool((_bits(table)[~named] == SENTINEL).all())
     assert _same(ws_a[:n_rows * seq_len * 640], ws_b[:n_rows * seq_len * 640])
     cot = torch.randn((n_rows, 128), generator=g).to(enc.device)
-    g_table = torch.full((1024, 128), float("nan"), device=enc.device)
+    g_table = torch.full((table_rows, 128), float("nan"), device=enc.device)
     g_table.index_copy_(0, rows, cot)
     want = enc.backward_raw(tokens, params, g_table.index_select(0, rows), ws_a)
     got = enc.backward_rows(tokens, params, g_table, rows, ws_b)

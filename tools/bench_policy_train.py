@@ -446,7 +446,8 @@ def part_update_parity(args):
         for vclip in (True, False):
             rows, _, _ = U._loss_compare(n, adv_mode, vclip, True)
             loss["adv_mode %d value_clip %d" % (adv_mode, vclip)] = pack(rows)
-    words = U._adam_sizes()[-1]
+    from mgx.fused_update import arena_layout
+    words = arena_layout(4)[1]
     adam = {case: pack(U._adam_compare(words, case)[0]) for case in ("clip", "noclip", "off")}
     worst = lambda d: max(v["ratio"] for c in d.values() for v in c.values())  # noqa: E731
     return dict(samples=n, arena_words=words, ppo_loss=loss, adam_step=adam, worst_ratio_ppo_loss=worst(loss),
